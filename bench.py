@@ -5,11 +5,27 @@ lists of length 300, batch 4096 per GPU (BASELINE.json configs[1]), on the HIP h
 
     python bench.py [--gpus N --steps K --warmup W]          # N=1 directly; N>1 starts its own N ranks
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # one rank per GPU
+    python bench.py --full                                   # plus every side measurement (below)
+    python bench.py --dump-outputs DIR                       # plus the last timed step's results as DIR/<name>.npy
 
 Launched with --gpus N > 1 and no WORLD_SIZE in the environment, this process never touches the GPU:
 it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child (fresh
 processes, one rank per GPU over RCCL), lets rank 0 print the JSON line and exits with the child's
 status.
+
+A plain run sets up, warms up, times the K steps of the headline precision mode, writes the --dump-outputs
+arrays if asked and prints the line: `metric`, `value`, `unit`, `ms_per_step`, `step_hip_events`, `dtype`,
+`config`, `collective`, `train_state`.  Everything else is measured only with --full: the `roofline`
+(attention launches timed in further training steps), the two sibling precision blocks (--other-steps), the
+HBM scan kernel (`hbm_kernel`), the reference's own batch sizes (`small_batch`, RLT_BENCH_SMALL=0 skips it)
+and the CPU oracle's `cpu_baseline` (--no-cpu-baseline skips it).  `--full` with the same arguments runs
+what this script ran before the option existed.
+
+--dump-outputs DIR (rank 0, after the timed steps, before anything --full adds): the model output(s), loss,
+cut positions, mean F1 / DCG, the flat gradient bucket and the flat parameters after the Adam step of the
+LAST timed step, float32 (float64 where the library computes in float64; integers as float64).  Inputs and
+initial weights are seeded, so the same arguments give the same inputs in every run.  At most 60 MB in all:
+an array above its share of that budget is replaced by a seeded sample of its flattened elements.
 
 Prints ONE JSON line (rank 0).  The top-level `value` / `ms_per_step` / `dtype` / `roofline` are the
 library's DEFAULT mode, `bf16x6`: f32 operands, accumulation and storage; every product of the GEMM
@@ -64,6 +80,34 @@ def synth_batch(batch, seq_len, n_feat, seed, device):
     y = (torch.rand(batch, seq_len, generator=g) < prob).float()
     y[y.sum(1) == 0, 0] = 1.0
     return x.to(device), y.to(device)
+
+
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs: each tensor of `tensors` (name -> tensor) as out_dir/<name>.npy.  float64 and integer tensors are
+    written as float64, all others as float32.  Smallest first, an array larger than its even share of what is left of
+    DUMP_BUDGET_BYTES becomes a seeded sample of its flattened elements (the same indices for the same size in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        arrays[name] = t.to("cpu", torch.float64 if wide else torch.float32).numpy()
+    left = DUMP_BUDGET_BYTES
+    order = sorted(arrays, key=lambda n: arrays[n].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, n, replace=False))
+            print(f"[bench] --dump-outputs: {name} is a seeded sample of {n} of its {a.size} elements", file=sys.stderr, flush=True)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def _cpu_model():
@@ -281,12 +325,17 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="ranked lists per GPU")
     ap.add_argument("--seq-len", type=int, default=300)
     ap.add_argument("--model", default="attncut", choices=["attncut", "choopy", "mtattncut", "mmoecut"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: roofline, the other precision modes, the HBM scan "
+                         "kernel, the reference's batch sizes and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--precision", default="bf16x6", choices=["bf16x6", "fp32", "bf16x3"],
                     help="MFMA product mode of the library for the headline figure (default bf16x6: fp32-faithful exact "
                          "three-way bf16 split, the library's default; fp32 = the f32 MFMA; bf16x3 = the opt-in fast mode)")
     ap.add_argument("--other-steps", "--fp32-steps", dest="other_steps", type=int, default=5,
-                    help="steps timed in each of the two OTHER precision modes after the headline loop (0: skip)")
+                    help="with --full: steps timed in each of the two OTHER precision modes after the headline loop (0: skip)")
     ap.add_argument("--cpu-sample-batch", type=int, default=512, help="batch of the vectorised-reward CPU sample")
     ap.add_argument("--cpu-loop-batch", type=int, default=32, help="batch of the loop-faithful CPU sample")
     # side configurations of SURVEY.md 8(d); the headline line uses none of them
@@ -383,11 +432,12 @@ def main():
         model.train()
         opt.zero_grad()
         out = model(x)
-        loss, _k, f1, dcg = Metric.step(crit, out, y)          # loss + cut metrics in one kernel pass, on device
+        loss, k, f1, dcg = Metric.step(crit, out, y)           # loss + cut metrics in one kernel pass, on device
         loss.backward()
         flat.all_reduce_grads()
         opt.step()
-        return loss, f1, dcg
+        outs = [o.detach() for o in out] if isinstance(out, (list, tuple)) else [out.detach()]
+        return loss, f1, dcg, outs, k
 
     def fence():
         torch.cuda.synchronize()
@@ -441,9 +491,17 @@ def main():
     headline = args.model == "attncut" and not args.buckets
     drop_tag = "true" if args.dropout > 0 else "false"
 
-    def run_mode(mode, n_steps, n_warm):
-        """Warm up, time n_steps (barrier + synchronize on both sides), then time the attention launches of further real
-        steps with HIP events; everything in the library's precision mode `mode`."""
+    def write_dump(state):
+        loss, f1, dcg, outs, k = state
+        arrays = {"output": outs[0]} if len(outs) == 1 else {f"output_{i}": o for i, o in enumerate(outs)}
+        arrays.update({"loss": loss, "cut_positions": k, "f1_mean": f1, "dcg_mean": dcg,
+                       "grads": flat.flat_grad, "params": flat.flat_param})
+        dump_outputs(args.dump_outputs, arrays)
+
+    def run_mode(mode, n_steps, n_warm, dump=False):
+        """Warm up, time n_steps (barrier + synchronize on both sides), with `dump` write the last step's results
+        (--dump-outputs), then, with --full, time the attention launches of further real steps with HIP events; everything
+        in the library's precision mode `mode`."""
         native.set_precision(mode)
         # every bucket is served at least once untimed (first use of a shape allocates its buffers)
         n_warm = n_warm if len(batches) == 1 else max(n_warm, len(batches))
@@ -453,10 +511,12 @@ def main():
             if rank == 0:
                 print(f"[bench] {mode}: warm-up step {i + 1}/{n_warm} done", file=sys.stderr, flush=True)
         elapsed, state, ev_stats = timed(n_steps)
-        vals = check_state(state, f"{n_steps} timed {mode} steps")
+        vals = check_state(state[:3], f"{n_steps} timed {mode} steps")
         if rank == 0:
             print(f"[bench] {mode}: {n_steps} timed steps, {elapsed / n_steps * 1e3:.1f} ms/step", file=sys.stderr, flush=True)
-        ksum = kernel_times(len(batches) * 3)
+            if dump:
+                write_dump(state)
+        ksum = kernel_times(len(batches) * 3) if args.full else None
         return {"mode": mode, "steps": n_steps, "elapsed": elapsed, "ms_per_step": elapsed / n_steps * 1e3,
                 "value": B * world * n_steps / elapsed, "state": vals, "ksum": ksum, "ev_stats": ev_stats}
 
@@ -536,8 +596,8 @@ def main():
                        "this mode), but its products carry 16 operand bits where the reference's fp32 carries 24 - never the headline",
              "bf16x6": "the library's default: GEMM family (csrc/gemm.hip gemm6*_kernel), list attention (csrc/attention6.hip, attention6n.hip) "
                        "and both BiLSTM recurrences (csrc/lstm6w.hip) on the exact three-way bf16 split, six MFMA products per fp32 product"}
-    main_res = run_mode(precision, args.steps, args.warmup)
-    other_res = [run_mode(m, args.other_steps, 1) for m in others] if args.other_steps > 0 else []
+    main_res = run_mode(precision, args.steps, args.warmup, dump=args.dump_outputs is not None)
+    other_res = [run_mode(m, args.other_steps, 1) for m in others] if args.full and args.other_steps > 0 else []
     native.set_precision(precision)
 
     collective = None
@@ -566,10 +626,11 @@ def main():
                                    f"full train step incl. Adam and cut metrics", "global_batch": B * world,
                        "seq_len": S if not args.buckets else lengths, "parallelism": f"dp{world}"},
             "collective": collective,
-            "roofline": roofline_block(main_res),
-            "hbm_kernel": hbm_kernel_both(S, dev) if world == 1 else None,
-            "train_state": {"loss": round(loss_v, 6), "f1": round(f1_v, 6), "dcg": round(dcg_v, 6)},
         }
+        if args.full:
+            out["roofline"] = roofline_block(main_res)
+            out["hbm_kernel"] = hbm_kernel_both(S, dev) if world == 1 else None
+        out["train_state"] = {"loss": round(loss_v, 6), "f1": round(f1_v, 6), "dcg": round(dcg_v, 6)}
         for res in other_res:
             m = res["mode"]
             out[BLOCK[m]] = {
@@ -579,9 +640,9 @@ def main():
                 "roofline": roofline_block(res),
                 "train_state": dict(zip(("loss", "f1", "dcg"), (round(v, 6) for v in res["state"]))),
                 "note": NOTES[m]}
-        if world == 1 and headline and args.dropout == 0 and os.environ.get("RLT_BENCH_SMALL", "1") != "0":
+        if args.full and world == 1 and headline and args.dropout == 0 and os.environ.get("RLT_BENCH_SMALL", "1") != "0":
             out["small_batch"] = small_batch_block(dev, S)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, args.cpu_sample_batch, args.cpu_loop_batch)
         print(json.dumps(out), flush=True)
     if use_dist:

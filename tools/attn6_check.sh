@@ -6,6 +6,5 @@ R=$GRAFT_REPO_ROOT
 python $R/tools/gpu_probe.py attention scale_ops models --precision=bf16x6 > $R/gpurun_out/${TAG}_probe.log 2>&1
 grep -n "FAIL\|ok, " $R/gpurun_out/${TAG}_probe.log | tail -8
 grep "attn .*B4096" $R/gpurun_out/${TAG}_probe.log
-python $R/bench.py --precision bf16x6 --no-cpu-baseline --other-steps 0 --steps 3 --warmup 1 > $R/gpurun_out/${TAG}_bench.json 2>/dev/null
-python -c "
-import json; d=json.load(open('$R/gpurun_out/${TAG}_bench.json')); r=d['roofline']; print('x6 step', d['ms_per_step'], 'dkv', r['launch_ms'], r['frac'], r['other_kernels_ms'])"
+python $R/bench.py --full --precision bf16x6 --no-cpu-baseline --other-steps 0 --steps 3 --warmup 1 2>/dev/null | python -c "
+import json, sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('x6 step', d['ms_per_step'], 'dkv', r['launch_ms'], r['frac'], r['other_kernels_ms'])"

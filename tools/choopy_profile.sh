@@ -5,7 +5,7 @@ set -e
 TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-ARGS="--precision bf16x6 --model choopy --batch 8192 --steps 2 --warmup 1 --no-cpu-baseline --other-steps 0"
+ARGS="--full --precision bf16x6 --model choopy --batch 8192 --steps 2 --warmup 1 --no-cpu-baseline --other-steps 0"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_choopy_bf16x6 -o p -- python3 $R/bench.py $ARGS > $O/${TAG}_prof_choopy_bf16x6.log 2>&1
 python3 $R/tools/trace_calls.py $(find $O/${TAG}_prof_choopy_bf16x6 -name p_kernel_trace.csv | head -1) > $O/${TAG}_choopy_bf16x6_per_call.txt

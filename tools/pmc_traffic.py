@@ -3,10 +3,10 @@
 
 On the GPU box:
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 then
-  python tools/pmc_traffic.py gpurun_out/pmc_fetch/p_counter_collection.csv gpurun_out/pmc_write/p_counter_collection.csv \
+  python tools/pmc_traffic.py $OUT/pmc_fetch/p_counter_collection.csv $OUT/pmc_write/p_counter_collection.csv \
          attn3_bwd_dkv_kernel "attncut b4096 s300 bf16x3" 6 > profiles/r02_pmc_traffic.json   # 6 = warm-up + steps + the 3 kernel-timing steps
 
 Units/corrections per /opt/skills/guides/MI355X_MICROARCH.md: both counters are in KB; on gfx950 FETCH_SIZE reports half
