@@ -173,6 +173,28 @@ int rlt_cut_metrics_ex(const float* p, const float* labels, const int32_t* k_in,
 int rlt_task_metrics(const float* labels, const float* pred, int B, int S,
                      double* dcg_out, double* auc_out, double* sums, void* stream);
 
+/* ------------------------------------------------------------------ truncation baselines
+ * The reference's Baseline/ notebooks (Oracle, Fixed-k, Greedy-k, Truncation_analysis) from one pass over labels (B,S),
+ * 0/1 in rank order, S in 1..1024.  With c_k = the sum of the first k labels and N = the sum of the list, for k = 1..S:
+ *   F1@k  = 2 p r / (p + r), p = c_k / k, r = c_k / N (0 if N = 0), 0 if p + r = 0: float64 in cal_F1's operation order with
+ *           correctly rounded division, so exactly tied values are bit-identical as in Python;
+ *   DCG@k = sum_{i<k} (label == 1 ? 1 : penalty) / log2(i + 2) in float64 (cal_DCG; the notebooks' penalty is -1);
+ *   k = 0 is an entry of every curve with value 0.
+ *   curves (3 x (S+1) float64, required): row 0 = sum over lists of F1@k, row 1 = of DCG@k, row 2 = of c_k, k = 0..S;
+ *   best_f1 / best_dcg (B) float64: each list's maximum over k = 0..S, best_f1_k / best_dcg_k (B) int32 its first maximum
+ *           (np.argmax); each may be NULL;
+ *   sums (3 doubles, may be NULL): sum of best F1, sum of best DCG, number of lists.
+ * accumulate = 1 ADDS this batch into curves and sums (a split streams through batch by batch with no host synchronisation),
+ * 0 overwrites them.  dcg_table: as for rlt_loss_metrics (8-byte aligned).  ws: rlt_truncation_curves_workspace(B, S) bytes,
+ * 8-byte aligned (0 for B <= 0: B must be positive, as for the other metric entry points).  Two launches: the pass (a
+ * wavefront owns whole lists - four per wavefront at S <= 64 - and keeps its per-k sums in registers; one float64 record per
+ * workgroup in ws) and a fixed-order column reduction of the records; no atomics, bitwise reproducible.
+ * Algorithmic bytes per list: read labels 4S (+ 24 B of per-list results). */
+size_t rlt_truncation_curves_workspace(int B, int S);
+int rlt_truncation_curves(const float* labels, int B, int S, double penalty, const void* dcg_table, int accumulate,
+                          double* curves, double* best_f1, int32_t* best_f1_k, double* best_dcg, int32_t* best_dcg_k,
+                          double* sums, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ dense contraction (M2-M7)
  * C[M,N] (+)= op(A) * op(B) (+ bias[N] + bias2[N]), optional ReLU.  fp32 in, fp32 accumulate on
  * the f32 MFMA (exact fp32 products, v_mfma_f32_32x32x2_f32).

@@ -956,6 +956,31 @@ def cut_metrics(p, labels, k_in=None, penalty=-1.0):
     return k, f1, dcg, sums
 
 
+def truncation_curves(labels, penalty=-1.0, curves=None, sums=None, per_list=False):
+    """The truncation curves of labels (B,S) float32 on device (rlt_truncation_curves): returns (curves (3, S+1) float64 = the
+    sums over lists of F1@k, DCG@k and c_k for k = 0..S, sums (3,) float64 = sum of best F1, sum of best DCG, list count,
+    per-list (best F1, its first k, best DCG, its first k) or None).  With `curves` and `sums` given, this batch is ADDED
+    into them (no host synchronisation), else they are fresh."""
+    if (curves is None) != (sums is None):
+        raise ValueError("truncation_curves: pass both `curves` and `sums` to accumulate, or neither")
+    B, S = labels.shape
+    dev = labels.device
+    accumulate = curves is not None
+    if not accumulate:
+        curves = torch.empty((3, S + 1), dtype=torch.float64, device=dev)
+        sums = torch.empty((3,), dtype=torch.float64, device=dev)
+    best = None
+    if per_list:
+        best = (torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev))
+    ws_bytes = query("rlt_truncation_curves_workspace", B, S)
+    ws = workspace(ws_bytes, dev)
+    bf, bfk, bd, bdk = best if per_list else (None,) * 4
+    call("rlt_truncation_curves", ptr(labels), B, S, float(penalty), ptr(dcg_table(dev)), int(accumulate), ptr(curves),
+         ptr(bf), ptr(bfk), ptr(bd), ptr(bdk), ptr(sums), ptr(ws), ws_bytes, stream())
+    return curves, sums, best
+
+
 def reward_matrix(labels, metric, tau=1.0, want_q=False, penalty=-1.0):
     B, S = labels.shape
     coef = dcg_coef(S, labels.device) if metric == N.METRIC_DCG else None

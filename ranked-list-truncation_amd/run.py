@@ -15,6 +15,8 @@ state_dict checkpoint on best test F1, run.py:153-232) and the same log lines.  
     all-reduce of the flat gradient bucket per step (rlt_hip/parallel.py);
   * the scalars the reference sends to tensorboardX (run.py:146,154-156,196-198) go, under the same tags, to
     `<tensorboard-dir>/scalars.jsonl` (and to a SummaryWriter when tensorboard is installed);
+  * --baselines 1: rank 0 first reports the truncation baselines of the reference's Baseline/ notebooks (Oracle, Fixed-k,
+    Greedy-k) on the run's own labels, per list length, on the device (utils/baselines.py);
   * not carried over: matplotlib plots and the hyper-parameter random search.
 """
 import argparse
@@ -100,6 +102,7 @@ class Trainer:
                                                            device=self.device, base=args.dataset_base, seed=args.seed)
         # the reference hard-codes 3 / 25 / 47 input features and 300 / 40 positions (run.py:34,60,70,86); here both
         # come from the files, and a mismatch with the reference's numbers is reported instead of mis-striding the LSTM
+        self.data = data
         feat = data.n_features
         if len(data.lengths) == 1:
             self.seq_len = data.lengths[0]
@@ -150,6 +153,7 @@ class Trainer:
         ops.set_seed_stream(self.rank)          # same torch seed on every rank, different dropout masks
         self.writer = ScalarLog(getattr(args, "tensorboard_dir", None) if self.rank == 0 else None)   # run.py:111
         self.history = []                       # per epoch: train / test (loss, f1, dcg) means
+        self.baseline_results = None            # --baselines 1: per list length, see baselines()
 
     # ------------------------------------------------------------------------------------------
     def _step(self, X, y, train):
@@ -237,7 +241,56 @@ class Trainer:
         self.model.load_state_dict(torch.load(self.model_path, map_location=self.device))
         logging.info('The best model has beed loaded from {}\n'.format(self.model_path))
 
+    def baselines(self):
+        """The reference's Baseline/ notebooks on this run's labels, for each list length of the test split: Oracle (each list's
+        best cut) and Fixed-k on the test lists, Greedy-k with its k from the train lists of the same length.  Logged, written
+        to the scalar log under baseline/... (step = the list length) and returned as {length: {...}}.  No collective."""
+        from utils.baselines import TruncationCurves
+        data = self.data
+        ks = [int(k) for k in str(self.args.fixed_k).split(',') if k.strip()]
+        single = len(data.lengths) == 1 and data.test_lengths == data.lengths
+        out = {}
+        for L in data.test_lengths:
+            if single:
+                y_train, y_test = data.gety_train(), data.gety_test()
+            else:
+                y_test = data.buckets['test'][L][1]
+                y_train = data.buckets['train'][L][1] if L in data.buckets['train'] else None
+            test = TruncationCurves(L, self.device).update(y_test)
+            f1, dcg = test.best_cut()
+            rec = {'n_test': test.n_lists, 'Oracle': {'f1': f1, 'dcg': dcg}, 'fixed_k': {}}
+            logging.info('\tBaseline Oracle (S = {}): f1 = {:.6f} | dcg = {:.6f}'.format(L, f1, dcg))
+            self.writer.add_scalar('baseline/Oracle_F1', f1, L)
+            self.writer.add_scalar('baseline/Oracle_DCG', dcg, L)
+            for k in ks:
+                if not 0 <= k <= L:
+                    logging.info('\tBaseline Fixed-k (S = {}, k = {}): k outside the list, skipped'.format(L, k))
+                    continue
+                f1, dcg = test.fixed_k(k)
+                rec['fixed_k'][str(k)] = {'f1': f1, 'dcg': dcg}
+                logging.info('\tBaseline Fixed-k (S = {}, k = {}): f1 = {:.6f} | dcg = {:.6f}'.format(L, k, f1, dcg))
+                self.writer.add_scalar('baseline/Fixed_k{}_F1'.format(k), f1, L)
+                self.writer.add_scalar('baseline/Fixed_k{}_DCG'.format(k), dcg, L)
+            if y_train is not None:
+                train = TruncationCurves(L, self.device).update(y_train)
+                k_f1, k_dcg = train.best_k()
+                f1, dcg = test.fixed_k((k_f1, k_dcg))
+                rec['n_train'] = train.n_lists
+                rec['greedy_k'] = {'k_f1': k_f1, 'k_dcg': k_dcg, 'f1': f1, 'dcg': dcg}
+                logging.info('\tBaseline Greedy-k (S = {}, k_f1 = {}, k_dcg = {}): f1 = {:.6f} | dcg = {:.6f}'.format(
+                    L, k_f1, k_dcg, f1, dcg))
+                self.writer.add_scalar('baseline/Greedy_k_F1', f1, L)
+                self.writer.add_scalar('baseline/Greedy_k_DCG', dcg, L)
+                self.writer.add_scalar('baseline/Greedy_k_kF1', k_f1, L)
+                self.writer.add_scalar('baseline/Greedy_k_kDCG', k_dcg, L)
+            else:
+                logging.info('\tBaseline Greedy-k (S = {}): no train lists of this length, skipped'.format(L))
+            out[str(L)] = rec
+        return out
+
     def run(self):
+        if self.args.baselines and self.rank == 0:
+            self.baseline_results = self.baselines()
         if self.rank == 0:
             logging.info('\nTrain the {} model: \n'.format(self.model_name))
         for epoch in range(self.epochs):
@@ -284,6 +337,10 @@ def build_parser():
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "
                         "replicas must stay bitwise identical)")
+    p.add_argument('--baselines', type=int, default=0, choices=(0, 1),
+                   help="1: rank 0 first reports the Oracle / Fixed-k / Greedy-k truncation baselines of the run's labels "
+                        "(the reference's Baseline/ notebooks), per list length")
+    p.add_argument('--fixed-k', type=str, default='5,10,30', help="comma-separated cut positions of the Fixed-k baseline")
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Truncation'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p
@@ -342,7 +399,7 @@ def main(argv=None):
             fin = lambda v: v if v is not None and math.isfinite(v) else None     # -inf (no test epoch) is not valid JSON
             json.dump({"history": trainer.history, "best_f1": fin(trainer.best_test_f1), "best_dcg": fin(trainer.best_test_dcg),
                        "best5_f1": fin(trainer.best5_f1), "best5_dcg": fin(trainer.best5_dcg), "best_epoch": trainer.best_epoch,
-                       "world": trainer.world}, f)
+                       "world": trainer.world, **({"baselines": trainer.baseline_results} if args.baselines else {})}, f)
     if args.param_dump_dir:
         import numpy as np
         os.makedirs(args.param_dump_dir, exist_ok=True)

@@ -145,6 +145,27 @@ def loss(S=300):
         print(f"loss, then metrics (4 launches) B{B} S{S}: {ms * 1e3:9.1f} us  {(nbytes + B * 8.0 * S) / ms / 1e6:8.1f} GB/s of its own bytes (p, labels read twice)", flush=True)
 
 
+def baselines(B=1048576, S=300):
+    """rlt_truncation_curves (the Oracle / Fixed-k / Greedy-k curves): 1,048,576 lists x 300 labels, robust04-shaped labels.
+    Algorithmic bytes: the labels, 4 S per list (the per-workgroup records and the curves are < 1 % of it).  Per-list outputs
+    off, as the streaming accumulator (utils/baselines.py) runs it."""
+    g = torch.Generator(device=dev).manual_seed(7)
+    prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+    y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+    curves = torch.zeros(3, S + 1, dtype=torch.float64, device=dev)
+    sums = torch.zeros(3, dtype=torch.float64, device=dev)
+    wsb = N.query("rlt_truncation_curves_workspace", B, S)
+    ws = torch.empty(wsb // 8 + 2, dtype=torch.float64, device=dev)
+    tab = ops.dcg_table(dev)
+    nbytes = 4.0 * B * S
+
+    def run():
+        call("rlt_truncation_curves", ptr(y), B, S, -1.0, ptr(tab), 0, ptr(curves), None, None, None, None, ptr(sums), ptr(ws), wsb, stream())
+    ms = timeit(run, reps=20, warm=3)
+    print(f"truncation curves B{B} S{S}: {ms * 1e3:9.1f} us  {nbytes / ms / 1e6:8.1f} GB/s algorithmic = {nbytes / ms / 1e6 / 8000:.3f} of 8 TB/s "
+          f"(records {wsb / 1e6:.1f} MB)", flush=True)
+
+
 def lstm(B=4096, S=300):
     T = S * B
     gates = torch.randn(T, 1024, device=dev) * 0.5
