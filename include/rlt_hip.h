@@ -459,6 +459,31 @@ int rlt_heads_bwd(const float* x, const float* w, const int* kinds, int n_heads,
                   float* dx, int accumulate_dx, float* dw, float* db,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ probe heads (the probing study)
+ * models/Classification.py:4-12 (TaskC), models/Rerank.py:4-12 (TaskR), models/Probe.py:30-53,102-122 (TowerClass /
+ * TowerRerank as the six probes of Probe), with their training losses of verify_BMT.py:37-44,71-80 and
+ * verify_probe.py:120-135,162-177: up to 8 heads Linear(E,1) on FROZEN position-major features x (S*B,E), each ending in
+ *   RLT_PROBE_BCE     Sigmoid -> nn.BCELoss() (mean over B*S; log clamped at -100; gradient = torch's BCE backward with its
+ *                     1e-12 clamp on s(1-s), then the sigmoid backward: a saturated sigmoid gets 0), or
+ *   RLT_PROBE_RERANK  Softmax over the S positions of a list -> RerankLoss (utils/losses.py:99-141): max(0, mean_{y=0} s -
+ *                     mean_{y=1} s + margin) over the whole batch, 0 with a zero gradient when a class is missing or the
+ *                     argument is <= 0 (the hinge of rlt_mt_terms, from the same arithmetic).
+ *   w (n_heads,E), b (n_heads), kinds (n_heads, host array); labels (B,S) exactly 0/1.  1 <= n_heads <= 8, 1 <= E <= 1024,
+ *   1 <= S <= 1024, B >= 1.
+ *   loss (n_heads): each head's own loss.  dw (n_heads,E), db (n_heads): each head's gradient of its own loss, overwritten;
+ *   both NULL for an evaluation call (loss and out are the same).  out (n_heads,B,S): the activations, or NULL.  No dx.
+ * ws: rlt_probe_heads_workspace(n_heads,S,B,E) bytes (0 for arguments out of range).  Three launches: one pass (a workgroup
+ * per list, online-softmax sums for the rerank heads) writing one record per list, a fixed-order column reduction of the
+ * records, and a one-workgroup finish (losses, hinge flag and 1/n_pos, 1/n_neg applied to dw); no atomics, bitwise
+ * reproducible.  Algorithmic bytes: read x 4*S*B*E once (+ labels 4*B*S, out 4*n*B*S, the records 4*B*(n*E + 3n + 2)). */
+#define RLT_PROBE_BCE    0
+#define RLT_PROBE_RERANK 1
+size_t rlt_probe_heads_workspace(int n_heads, int S, int B, int E);
+int rlt_probe_heads(const float* x, const float* w, const float* b, const int* kinds, int n_heads,
+                    int S, int B, int E, const float* labels, float margin,
+                    float* loss, float* dw, float* db, float* out,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ MMOE gates / mixture (M7)
  * models/MMOECut.py:93-94: gate[t][b][:] = softmax_e( flatten_s(h[b]) @ w_gate[t] ), h the BiLSTM
  * output (position-major (S*B,C), C = 256), w_gate[t]: (S*C, n_e) row index s*C + c.

@@ -11,6 +11,7 @@
 // Algorithmic bytes per list (fp32): read p 4S + labels 4S, write dL/dp 4S (+ 4 B loss) = 3.6 KB at
 // S = 300.
 #include "common.h"
+#include "mt_terms.h"
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -705,12 +706,7 @@ __global__ __launch_bounds__(256) void mt_partial_kernel(const float* rerank, co
             if (t == 1.f) { s_pos += s; n_pos += 1.f; }
             if (t == 0.f) { s_neg += s; n_neg += 1.f; }
         }
-        if (cls) {   // torch binary_cross_entropy: logs clamped at -100
-            const float c = cls[i];
-            const float l1 = fmaxf(logf(c), -100.f);
-            const float l0 = fmaxf(log1pf(-c), -100.f);
-            bce += (t - 1.f) * l0 - t * l1;
-        }
+        if (cls) bce += rlt_bce_term(cls[i], t);   // torch binary_cross_entropy: logs clamped at -100
     }
     float v[5] = {s_pos, n_pos, s_neg, n_neg, bce};
     __shared__ float sm[4][5];
@@ -735,10 +731,7 @@ __global__ __launch_bounds__(64) void mt_final_kernel(const float* partial, int 
     for (int k = 0; k < 5; ++k) v[k] = wave_sum(v[k]);
     if (lane == 0) {
         float hinge = 0.f, gpos = 0.f, gneg = 0.f;
-        if (has_rerank && v[1] > 0 && v[3] > 0) {            // utils/losses.py:136-141
-            const float gap = (float)(v[2] / v[3]) - (float)(v[0] / v[1]) + margin;
-            if (gap > 0.f) { hinge = gap; gpos = (float)(-1.0 / v[1]); gneg = (float)(1.0 / v[3]); }
-        }
+        if (has_rerank) rlt_rerank_hinge(v[0], v[1], v[2], v[3], margin, hinge, gpos, gneg);   // utils/losses.py:136-141
         terms[0] = hinge;
         terms[1] = has_cls ? (float)(v[4] / n_elem) : 0.f;
         terms[2] = gpos;
@@ -755,10 +748,7 @@ __global__ __launch_bounds__(256) void mt_bwd_kernel(const float* cls, const flo
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float t = y[i];
         if (d_rerank) d_rerank[i] = (t == 1.f) ? gpos : ((t == 0.f) ? gneg : 0.f);
-        if (d_class) {   // torch binary_cross_entropy_backward: (x - t) / max((1-x)x, 1e-12)
-            const float c = cls[i];
-            d_class[i] = (c - t) / fmaxf((1.f - c) * c, 1e-12f) * cscale;
-        }
+        if (d_class) d_class[i] = rlt_bce_dgrad(cls[i], t) * cscale;   // torch binary_cross_entropy_backward
     }
 }
 

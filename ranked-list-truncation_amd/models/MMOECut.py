@@ -35,6 +35,7 @@ class TowerCut(_Tower):
 
 class TowerClass(_Tower):
     kind = N.HEAD_SIGMOID
+    probe_kind = N.PROBE_BCE       # as a probe (models/Probe.py): trained with nn.BCELoss
 
     def __init__(self, d_model):
         super().__init__(d_model, "classification_layer")
@@ -42,6 +43,7 @@ class TowerClass(_Tower):
 
 class TowerRerank(_Tower):
     kind = N.HEAD_SOFTMAX          # the MMOE rerank tower ends in a softmax over positions (MMOECut.py:46-49)
+    probe_kind = N.PROBE_RERANK    # as a probe (models/Probe.py): trained with RerankLoss
 
     def __init__(self, d_model):
         super().__init__(d_model, "rerank_layer")
@@ -72,6 +74,11 @@ class MMOECut(nn.Module):
         self.towers = nn.ModuleList(towers)
 
     def forward(self, x):
+        return self.forward_pm(x)[2]
+
+    def forward_pm(self, x):
+        """(BiLSTM output h, expert outputs, tower outputs): h and the experts position-major (S*B, d_model), the towers
+        (B,S,1) each."""
         x = C.check_input(x)
         drop_p = C.check_dropout(self, self.dropout)
         B, S, _ = x.shape
@@ -82,7 +89,7 @@ class MMOECut(nn.Module):
         gates = ops.MMOEGateFn.apply(h, S, B, *self.w_gates)                              # (n_tasks,B,n_e)
         mixed = ops.MMOEMixFn.apply(gates, S, B, *expert_out)                             # (n_tasks,S*B,E)
         outs = []
-        for t, tower in enumerate(self.towers):
+        for t, tower in zip(range(mixed.shape[0]), self.towers):     # zip: as many towers as gates
             lin = tower.linear
             outs.append(ops.heads(mixed[t], [lin.weight], [lin.bias], [tower.kind], S, B)[0])
-        return outs
+        return h, expert_out, outs

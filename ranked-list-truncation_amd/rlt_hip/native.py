@@ -18,6 +18,7 @@ METRIC_F1, METRIC_DCG = 0, 1
 LOSS_EXPECT, LOSS_CE, LOSS_KL, LOSS_JS = 0, 1, 2, 3
 GEMM_RELU, GEMM_ACCUMULATE = 1, 2
 HEAD_SOFTMAX, HEAD_SIGMOID, HEAD_IDENTITY = 0, 1, 2
+PROBE_BCE, PROBE_RERANK = 0, 1
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
 
@@ -47,6 +48,8 @@ _SIGNATURES = {
     "rlt_task_metrics": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "rlt_truncation_curves_workspace": (c_size_t, [c_int, c_int]),
     "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "rlt_probe_heads_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rlt_probe_heads": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
     "rlt_pair_softmax_fwd": (c_int, [P, c_int, c_int, c_float, c_uint32, P, P]),
     "rlt_pair_softmax_bwd": (c_int, [P, P, c_int, c_int, c_float, c_uint32, P, P]),
     "rlt_bicut_loss": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),

@@ -946,6 +946,62 @@ class RerankLossFn(Function):
         return d.view(ctx.sshape), None, None
 
 
+
+class ProbeHeadsFn(Function):
+    """Probe heads on frozen features (rlt_probe_heads): x (S*B,E) -> per-head losses (n,) and activations (n,B,S), with
+    each head's gradient of its own loss formed in the same pass; backward only scales it by the incoming go[h]."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, labels, kinds, S, B, margin, want_out):
+        n, E = w.shape
+        loss = _empty((n,), x)
+        out = _empty((n, B, S), x) if want_out else None
+        train = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dw = _empty((n, E), x) if train else None
+        db = _empty((n,), x) if train else None
+        karr = (N.c_int * n)(*kinds)
+        ws_bytes = query("rlt_probe_heads_workspace", n, S, B, E)
+        ws = workspace(ws_bytes, x.device)
+        call("rlt_probe_heads", ptr(x), ptr(w), ptr(b), karr, n, S, B, E, ptr(labels), float(margin), ptr(loss), ptr(dw),
+             ptr(db), ptr(out), ptr(ws), ws_bytes, stream())
+        ctx.save_for_backward(dw, db)
+        if out is None:
+            return loss
+        ctx.mark_non_differentiable(out)
+        return loss, out
+
+    @staticmethod
+    def backward(ctx, go, *_unused):
+        dw, db = ctx.saved_tensors
+        go = N.f32c(go)
+        return None, dw * go[:, None], db * go, None, None, None, None, None, None
+
+
+def probe_heads(x_pm, weights, biases, kinds, labels, S, B, margin=5e-4, want_out=True):
+    """Probe heads Linear(E,1) -> Sigmoid -> BCELoss (N.PROBE_BCE) or -> Softmax over positions -> RerankLoss
+    (N.PROBE_RERANK) on frozen position-major features x_pm (S*B,E); labels (B,S).  weights: list of (1,E) or (E,)
+    parameters, biases: list of (1,) parameters.  Returns (losses (n,), [activations (B,S,1) per head] or None); the losses
+    backpropagate into the weights and biases.  No host synchronisation.
+    Labels must be exactly 0 or 1.  The rerank gradient is formed as (gpos - gneg) s_i (y_i - V), an identity that holds
+    only for 0/1 labels; with other values it differs from RerankLoss's (and rlt_mt_terms'), which give such entries no
+    gradient of their own.  Nothing checks this (a check would cost a host synchronisation)."""
+    if x_pm.requires_grad:
+        raise ValueError("probe_heads: the features must be frozen (detach them or draw them under torch.no_grad())")
+    N.require_cuda(x_pm, labels)
+    kinds = [int(k) for k in kinds]
+    if any(k not in (N.PROBE_BCE, N.PROBE_RERANK) for k in kinds):
+        raise ValueError(f"probe_heads: unknown head kind in {kinds}")
+    if not (len(weights) == len(biases) == len(kinds)):
+        raise ValueError("probe_heads: one weight, bias and kind per head")
+    w = torch.cat([wi.reshape(1, -1) for wi in weights], dim=0) if len(weights) > 1 else weights[0].reshape(1, -1)
+    b = torch.cat([bi.reshape(1) for bi in biases], dim=0) if len(biases) > 1 else biases[0].reshape(1)
+    res = ProbeHeadsFn.apply(N.f32c(x_pm), N.f32c(w), N.f32c(b), N.f32c(labels), kinds, S, B, margin, bool(want_out))
+    if not want_out:
+        return res, None
+    loss, out = res
+    return loss, [out[i].unsqueeze(2) for i in range(len(kinds))]
+
+
 # ------------------------------------------------------------------------------ metrics
 def cut_metrics(p, labels, k_in=None, penalty=-1.0):
     """Per-list (k, F1@k, DCG@k) on device; p (B,S) or (B,S,1), labels (B,S).  Returns tensors."""

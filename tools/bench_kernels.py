@@ -166,6 +166,52 @@ def baselines(B=1048576, S=300):
           f"(records {wsb / 1e6:.1f} MB)", flush=True)
 
 
+def probe(B=4096, S=300, E=256):
+    """rlt_probe_heads (the probing study's fused probe pass) against the composed path on the same data: one BCE and one
+    rerank head on frozen position-major features x (S*B, E) = 1.26 GB.  Fused: x read once, no dx.  Composed: rlt_heads_fwd
+    (x read) + rlt_mt_terms + rlt_mt_terms_bwd + rlt_heads_bwd (x read again, a dx nobody uses written): >= 3 x 4 S B E bytes.
+    GB/s counts each path's algorithmic bytes; the fraction is of 8 TB/s."""
+    T = S * B
+    x = torch.randn(T, E, device=dev)
+    g = torch.Generator(device=dev).manual_seed(7)
+    prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+    y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+    w = torch.randn(2, E, device=dev) / E ** 0.5
+    b = torch.zeros(2, device=dev)
+    loss, dw, db, out = torch.empty(2, device=dev), torch.empty(2, E, device=dev), torch.empty(2, device=dev), torch.empty(2, B, S, device=dev)
+    karr = (N.c_int * 2)(N.PROBE_BCE, N.PROBE_RERANK)
+    wsb = N.query("rlt_probe_heads_workspace", 2, S, B, E)
+    ws = N.workspace(wsb, dev)
+
+    def fused():
+        call("rlt_probe_heads", ptr(x), ptr(w), ptr(b), karr, 2, S, B, E, ptr(y), 5e-4, ptr(loss), ptr(dw), ptr(db), ptr(out),
+             ptr(ws), wsb, stream())
+    hk = (N.c_int * 2)(N.HEAD_SIGMOID, N.HEAD_SOFTMAX)
+    terms = torch.empty(4, device=dev)
+    tws_b = N.query("rlt_mt_terms_workspace", B, S)
+    tws = N.workspace(tws_b, dev)
+    dout = torch.empty(2, B, S, device=dev)
+    dx = torch.empty(T, E, device=dev)
+    hws_b = N.query("rlt_heads_bwd_workspace", 2, S, B, E)
+    hws = N.workspace(hws_b, dev)
+    dw2, db2 = torch.empty(2, E, device=dev), torch.empty(2, device=dev)
+
+    def composed():
+        call("rlt_heads_fwd", ptr(x), ptr(w), ptr(b), hk, 2, S, B, E, ptr(out), stream())
+        call("rlt_mt_terms", ptr(out[1]), ptr(out[0]), ptr(y), B, S, 5e-4, ptr(terms), ptr(tws), tws_b, stream())
+        call("rlt_mt_terms_bwd", ptr(out[0]), ptr(y), ptr(terms), B, S, 1.0, 1.0, None, ptr(dout[1]), ptr(dout[0]), stream())
+        call("rlt_heads_bwd", ptr(x), ptr(w), hk, 2, ptr(out), ptr(dout), S, B, E, ptr(dx), 0, ptr(dw2), ptr(db2), ptr(hws),
+             hws_b, stream())
+    xb = 4.0 * T * E
+    fb = xb + 4.0 * B * S * 3 + wsb
+    cb = 3 * xb + 4.0 * B * S * 12
+    mf = timeit(fused, reps=10, warm=2)
+    mc = timeit(composed, reps=10, warm=2)
+    print(f"probe fused    B{B} S{S} E{E} 2 heads: {mf * 1e3:9.1f} us  {fb / mf / 1e6:8.1f} GB/s = {fb / mf / 1e6 / 8000:.3f} of 8 TB/s", flush=True)
+    print(f"probe composed B{B} S{S} E{E} 2 heads: {mc * 1e3:9.1f} us  {cb / mc / 1e6:8.1f} GB/s = {cb / mc / 1e6 / 8000:.3f} of 8 TB/s", flush=True)
+    print(f"probe fused / composed speed-up: {mc / mf:.2f}x", flush=True)
+
+
 def lstm(B=4096, S=300):
     T = S * B
     gates = torch.randn(T, 1024, device=dev) * 0.5
