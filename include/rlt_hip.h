@@ -484,6 +484,29 @@ int rlt_probe_heads(const float* x, const float* w, const float* b, const int* k
                     float* loss, float* dw, float* db, float* out,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ neighbour-similarity input features (AttnCut's statistics)
+ * data_prep/data_review.ipynb (cos_simi, simi_docs, simi_list) and data_prep/document_statics.ipynb (cos_similarity,
+ * neighbor_sim): for every position of a ranked list the cosine similarity of its document to the documents ranked next to it,
+ * once over the tf-idf vectors and once over the doc2vec vectors.
+ *   sim(a, b) = (a . b) / (|a| |b|), 0 when the denominator is 0 or the quotient is NaN;
+ *   position 0: sim(0, 1);  position S-1: sim(S-2, S-1);  position i in between: (sim(i-1, i) + sim(i, i+1)) / 2.
+ * doc_ids (B,S) int32: the row of each ranked document in the tables, rank order; every id in [0, n_docs) - the caller's duty,
+ * the kernel does not test it.  B >= 1, S >= 2, B * S < 2^31.
+ * Dense table d2v (n_docs, D) float32, row stride ld_d2v >= D floats, D in 1..1024.  Sparse table in CSR: indptr (n_docs + 1)
+ * int64, indices int32 strictly ascending within a row, values float64 (8-byte aligned); a row may be empty or of any length.
+ * Either table may be NULL (the sparse one: all three pointers NULL), not both.
+ * out: float32, position (b, i) at out + (b * S + i) * ld_out + col; the tf-idf similarity first, then the doc2vec one (one
+ * column only when a table is NULL): col = 1, ld_out = 3 writes columns 1..2 of the packed model input X (B,S,3) in place.
+ * Every sum, the square roots and the division are float64 (the doc2vec column too: products of two float32 are exact there);
+ * the half-sum is rounded to float32 once.  One launch, no workspace: a wavefront owns 64 positions of a list, walks their
+ * documents in rank order (one document of overlap on either side), keeps the previous dense row and both squared norms in
+ * registers and the previous sparse row in LDS (rows over 128 entries are searched in place), and intersects two sparse rows
+ * by a binary search per entry.  Fixed reduction order, no atomics: bitwise reproducible.
+ * Algorithmic bytes per position: 4 (id) + 4 D (dense row) + 12 nnz (sparse row) + 8 (two outputs). */
+int rlt_neighbor_features(const int32_t* doc_ids, int B, int S, int n_docs, const float* d2v, int D, int ld_d2v,
+                          const int64_t* indptr, const int32_t* indices, const double* values,
+                          float* out, int ld_out, int col, void* stream);
+
 /* ------------------------------------------------------------------ MMOE gates / mixture (M7)
  * models/MMOECut.py:93-94: gate[t][b][:] = softmax_e( flatten_s(h[b]) @ w_gate[t] ), h the BiLSTM
  * output (position-major (S*B,C), C = 256), w_gate[t]: (S*C, n_e) row index s*C + c.

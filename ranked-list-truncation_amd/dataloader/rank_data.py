@@ -68,15 +68,22 @@ def _pin(t):
 
 
 class RankData:
-    """`stats_dir`: None (Choopy family: score only), 'attncut' or 'mtcut'."""
+    """`stats_dir`: None (Choopy family: score only), 'attncut' or 'mtcut'.  `doc_table` (a doc_features.DocTable over the
+    documents of both splits): the neighbour-similarity statistics are computed from it on the GPU instead of read from
+    `stats_dir`."""
 
-    def __init__(self, retrieve_data="robust04", dataset_name="bm25", with_stats=True, base=None, stats_dir="attncut"):
+    def __init__(self, retrieve_data="robust04", dataset_name="bm25", with_stats=True, base=None, stats_dir="attncut",
+                 doc_table=None):
         base = os.path.join(base or DATASET_BASE, retrieve_data)
         gt = _load(os.path.join(base, "gt.pkl"))
         self.buckets = {}
         for split in ("train", "test"):
             raw = _load(os.path.join(base, f"{dataset_name}_{split}.pkl"))
-            stats = _load(os.path.join(base, stats_dir, f"{dataset_name}_{split}.pkl")) if with_stats else None
+            if with_stats and doc_table is not None:
+                from .doc_features import neighbor_stats
+                stats = neighbor_stats(raw, doc_table)
+            else:
+                stats = _load(os.path.join(base, stats_dir, f"{dataset_name}_{split}.pkl")) if with_stats else None
             self.buckets[split] = {s: (_pin(torch.from_numpy(x)), _pin(torch.from_numpy(y)), qids)
                                    for s, (x, y, qids) in sorted(_pack(raw, stats, gt).items())}
         # one feature width for every bucket of both splits (the statistics width is inferred per bucket from its first
@@ -209,8 +216,9 @@ def _loaders(rank_data, batch_size, device, seed):
             BatchLoader(pairs("test"), batch_size, True, device, seed + 1), rank_data)
 
 
-def attncut_dataloader(retrieve_data="robust04", dataset_name="bm25", batch_size=20, device=None, base=None, seed=None):
-    return _loaders(RankData(retrieve_data, dataset_name, True, base, "attncut"), batch_size, device, seed)
+def attncut_dataloader(retrieve_data="robust04", dataset_name="bm25", batch_size=20, device=None, base=None, seed=None,
+                       doc_table=None):
+    return _loaders(RankData(retrieve_data, dataset_name, True, base, "attncut", doc_table), batch_size, device, seed)
 
 
 def choopy_dataloader(retrieve_data="robust04", dataset_name="bm25", batch_size=20, device=None, base=None, seed=None):

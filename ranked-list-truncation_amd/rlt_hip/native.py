@@ -50,6 +50,7 @@ _SIGNATURES = {
     "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_probe_heads_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rlt_probe_heads": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
+    "rlt_neighbor_features": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_int, c_int, P]),
     "rlt_pair_softmax_fwd": (c_int, [P, c_int, c_int, c_float, c_uint32, P, P]),
     "rlt_pair_softmax_bwd": (c_int, [P, P, c_int, c_int, c_float, c_uint32, P, P]),
     "rlt_bicut_loss": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),

@@ -1037,6 +1037,47 @@ def truncation_curves(labels, penalty=-1.0, curves=None, sums=None, per_list=Fal
     return curves, sums, best
 
 
+def neighbor_features(doc_ids, table, out=None, col=0, validate=True):
+    """AttnCut's neighbour-similarity statistics (rlt_neighbor_features): doc_ids (B,S) int32 rows of `table` in rank order ->
+    per position the cosine similarity to the neighbouring documents, the tf-idf column first, then the doc2vec one.
+    `table`: an object with `n_docs`, `d2v` ((n_docs,D) float32 or None) and `indptr` / `indices` / `values` (int64 / int32 /
+    float64 CSR, or None) on the device of doc_ids - dataloader.doc_features.DocTable.to(device) is one.  `out`: a float32
+    tensor (B,S,F) whose columns col.. receive the result in place (F = 3, col = 1: the packed model input), or None for a
+    fresh (B,S,columns).  An id outside [0, n_docs) raises ValueError; that test is the one host synchronisation here and
+    `validate=False` leaves it out for ids the caller built from the table's own map."""
+    if doc_ids.dim() != 2 or doc_ids.dtype != torch.int32:
+        raise ValueError("neighbor_features: doc_ids must be a (B, S) int32 tensor")
+    B, S = doc_ids.shape
+    if B < 1 or S < 2:
+        raise ValueError(f"neighbor_features: needs at least one list of at least 2 documents, got {B} x {S}")
+    d2v, indptr, indices, values = table.d2v, table.indptr, table.indices, table.values
+    if d2v is None and indptr is None:
+        raise ValueError("neighbor_features: the table holds neither tf-idf rows nor doc2vec rows")
+    N.require_cuda(doc_ids, d2v, indptr, indices, values, out)
+    n_docs = int(table.n_docs)
+    if d2v is not None and (d2v.dtype != torch.float32 or d2v.dim() != 2 or d2v.shape[0] != n_docs or d2v.stride(1) != 1):
+        raise ValueError("neighbor_features: d2v must be (n_docs, D) float32 with unit column stride")
+    if indptr is not None and (indptr.dtype != torch.int64 or indices.dtype != torch.int32 or values.dtype != torch.float64
+                               or indptr.numel() != n_docs + 1 or not (indptr.is_contiguous() and indices.is_contiguous()
+                                                                       and values.is_contiguous())):
+        raise ValueError("neighbor_features: CSR arrays must be contiguous indptr (n_docs+1) int64, indices int32, values float64")
+    doc_ids = doc_ids if doc_ids.is_contiguous() else doc_ids.contiguous()
+    if validate:
+        lo, hi = torch.aminmax(doc_ids)
+        if int(lo) < 0 or int(hi) >= n_docs:
+            raise ValueError(f"neighbor_features: document row outside [0, {n_docs}): min {int(lo)}, max {int(hi)}")
+    ncol = (d2v is not None) + (indptr is not None)
+    if out is None:
+        out = torch.empty((B, S, ncol), dtype=torch.float32, device=doc_ids.device)
+        col = 0
+    if out.dtype != torch.float32 or out.dim() != 3 or tuple(out.shape[:2]) != (B, S) or out.stride(2) != 1 \
+            or (B > 1 and out.stride(0) != S * out.stride(1)) or col < 0 or col + ncol > out.shape[2]:
+        raise ValueError(f"neighbor_features: out must be float32 (B, S, F) with rows of equal stride and F >= col + {ncol}")
+    call("rlt_neighbor_features", ptr(doc_ids), B, S, n_docs, ptr(d2v), 0 if d2v is None else d2v.shape[1],
+         0 if d2v is None else d2v.stride(0), ptr(indptr), ptr(indices), ptr(values), ptr(out), out.stride(1), int(col), stream())
+    return out
+
+
 def reward_matrix(labels, metric, tau=1.0, want_q=False, penalty=-1.0):
     B, S = labels.shape
     coef = dcg_coef(S, labels.device) if metric == N.METRIC_DCG else None

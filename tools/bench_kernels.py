@@ -483,6 +483,69 @@ def dq1_stamps():
     dkv1_stamps(which="dq")
 
 
+def features(B=4096, S=300, n_docs=131072, D=200, n_terms=231448, rounds=25):
+    """rlt_neighbor_features (AttnCut's neighbour-similarity statistics, both columns written into the packed model input) over
+    4096 lists x 300 from a table of 131,072 documents: doc2vec rows of 200 float32, tf-idf rows drawn from the robust-like
+    profile of tools/make_feature_golden.py.  Beside it, alternating in the same process, a torch composition of the doc2vec
+    column ALONE (index_select of the rows, product, sum, norms, divide): what the library offered before this kernel.
+    HIP-event time per launch, median over `rounds` launches of each after warm-up.  Algorithmic bytes per position: 4 (id)
+    + 4 D (dense row) + 12 nnz (sparse row) + 8 (two outputs)."""
+    import types
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from make_feature_golden import robust_like_table
+    rs = np.random.RandomState(20261016)
+    indptr, indices, values = robust_like_table(rs, n_docs, n_terms)
+    d2v_h = (rs.standard_normal((n_docs, D)) * 0.3).astype(np.float32)
+    ids_h = rs.randint(0, n_docs, (B, S)).astype(np.int32)
+    table = types.SimpleNamespace(n_docs=n_docs, indptr=torch.from_numpy(indptr).to(dev), indices=torch.from_numpy(indices).to(dev),
+                                  values=torch.from_numpy(values).to(dev), d2v=torch.from_numpy(d2v_h).to(dev))
+    ids = torch.from_numpy(ids_h).to(dev)
+    X = torch.zeros(B, S, 3, device=dev)
+    nnz = int(np.diff(indptr)[ids_h].sum())
+    nbytes = float(B * S * (4 + 4 * D + 8) + 12 * nnz)
+
+    def fused():
+        ops.neighbor_features(ids, table, out=X, col=1, validate=False)
+
+    flat = ids.reshape(-1).long()
+    first = (torch.arange(B * S, device=dev) % S) == 0
+    last = (torch.arange(B * S, device=dev) % S) == S - 1
+
+    def composed():
+        x = table.d2v.index_select(0, flat)                     # (B*S, D): the gathered copy
+        nrm = torch.linalg.vector_norm(x, dim=1)
+        num = (x[:-1] * x[1:]).sum(1)
+        den = nrm[:-1] * nrm[1:]
+        sim = torch.nan_to_num(torch.where(den != 0, num / den, torch.zeros_like(num)), nan=0.0)
+        right = torch.cat([sim, sim[-1:]])                      # sim(i, i+1) at i
+        left = torch.cat([sim[:1], sim])                        # sim(i-1, i) at i
+        out = torch.where(first, right, (left + right) / 2)
+        return torch.where(last, left, out).view(B, S)
+
+    for _ in range(3):
+        fused()
+        ref = composed()
+    torch.cuda.synchronize()
+    diff = float((X[:, :, 2] - ref).abs().max())
+    t = {"fused": [], "composed": []}
+    for _ in range(rounds):
+        for name, fn in (("fused", fused), ("composed", composed)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            t[name].append(a.elapsed_time(b) * 1e3)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    print(f"neighbor features B{B} S{S} D{D} docs{n_docs} mean nnz {nnz / (B * S):.1f}: fused two columns {med['fused']:9.1f} us "
+          f"(min {min(t['fused']):.1f}, max {max(t['fused']):.1f}; {nbytes / med['fused'] / 1e3:8.1f} GB/s algorithmic = "
+          f"{nbytes / med['fused'] / 1e3 / 8000:.3f} of 8 TB/s; {B / med['fused'] * 1e6:.3e} lists/s)", flush=True)
+    print(f"    torch composition, doc2vec column alone      {med['composed']:9.1f} us (min {min(t['composed']):.1f}, max "
+          f"{max(t['composed']):.1f}); ratio composed / fused = {med['composed'] / med['fused']:.2f}; max |fused - composed| on "
+          f"that column {diff:.2e}; median over {rounds} alternating launches", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
