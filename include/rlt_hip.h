@@ -433,6 +433,70 @@ int rlt_bilstm_generic_bwd(const float* x, int I, int hidden, const rlt_lstm_lay
                            const float* dh_out, int S, int B, void* stash, size_t stash_bytes, float* dx,
                            const rlt_lstm_layer_grads* g, void* ws, size_t ws_bytes, int precision, void* stream);
 
+/* ------------------------------------------------------------------ sparse layer-0 input (BiCut on its bag-of-words input)
+ * models/Bicut.py:6,10 (BiCut(input_size=231449): nn.LSTM over the document vectors), data_prep/document_statics.ipynb
+ * sections "bicut统计数据获取" / "Bicut输入数据" (per ranked document [token count, distinct-token count, bag-of-words vector]),
+ * dataloader/split_bicut_data.py:21-24 (the retrieval score put in front) and dataloader/bicut_dataloader.py:15-40 (one
+ * densified 300 x 231,451 pickle per query, `.float()`): the input projection x W_ih^T + b_ih + b_hh of BiLSTM layer 0 and
+ * its weight gradient, with x never densified.  A token row t = s*B + b is `Dn` leading dense columns plus ONE row of a
+ * device-resident CSR table; the layer-0 input width is I = Dn + V.
+ *   dense (B,S,Dn) float32 and ids (B,S) int32 (row of each ranked document in the table) in the reference's (B,S) layout;
+ *   table: indptr (n_docs+1) int64, indices int32 (term ids in [0,V), strictly ascending within a row), values float32; a row
+ *   may be empty; total nonzeros are bounded by int64 only.  1 <= Dn <= 16, B*S < 2^31, Dn + V < 2^31.
+ * The two layer-0 input weights are COLUMN-MAJOR: wt (I, 512) per direction, wt[c*512 + g] = weight_ih_l0[g, c] - the memory
+ * of a (512, I) tensor with strides (1, 512) - so that one nonzero reads and one gradient column writes 2 KB contiguous per
+ * direction (row-major it would be 1024 reads 4*I bytes apart per nonzero).
+ *   fwd: gates[t, dir, :] = b_ih[dir] + b_hh[dir] + sum_{c<Dn} dense[t,c] wt[dir][c,:] + sum_{j in row ids[t]} values[j]
+ *        wt[dir][Dn + indices[j], :], one fp32 fma chain per gate in exactly that order, into the (S*B, 2, 512) buffer that
+ *        rlt_bilstm_rec_fwd consumes.  One launch, a workgroup per token row.
+ *   bwd: from dgates (S*B, 2, 512) = the pre-activation gate gradients rlt_bilstm_rec_bwd leaves: dwt (I, 512) per direction
+ *        with EVERY column written (=) - columns of terms absent from the batch are exact zeros -, db_ih = db_hh =
+ *        colsum(dgates).  There is no dx: the input is data.  Needs two things beyond the forward's:
+ *        - perm (S*B) int32: the token rows t ordered by (ids[t], t) ascending - a stable sort of the position-major ids;
+ *        - the table's static term -> rows index, built once by the host: col_ptr (V+1) int64 / col_rows int32 / col_vals
+ *          float32 = the table transposed (per term its rows ascending), cut into chunks of RLT_SPARSE_CHUNK entries:
+ *          chunk_ptr (V+1) int32 = first chunk of each term, every term owning max(1, ceil(entries / RLT_SPARSE_CHUNK))
+ *          consecutive chunks; chunk_col (n_chunks) int32 = the term of each chunk; multi_cols (n_multi) int32 = the terms
+ *          that own more than one chunk, ascending.
+ *        One workgroup per chunk adds its entries in index order (a row occurring at several token rows: in `perm` order);
+ *        chunk 0 of a term writes the column, later chunks write partial sums into ws that one more launch adds in chunk
+ *        order; the dense columns and biases are partial sums over blocks of 32 token rows reduced in block order.  No float
+ *        atomics: bitwise reproducible.  ws: rlt_sparse_inproj_workspace(S, B, Dn, n_docs, V, n_chunks) bytes (0 for
+ *        arguments out of range), 16-byte aligned.
+ * A table row outside [0, n_docs), a term id outside [0, V) and a perm entry outside [0, S*B) are never dereferenced: they
+ * contribute nothing (the Python binding tests the ids and raises, as for rlt_neighbor_features).  The static index is trusted
+ * as far as its own arrays go (col_ptr within col_rows / col_vals); a chunk table that does not fit V and n_chunks writes nothing.
+ * Errors before any launch: RLT_E_ARG (a NULL member or pointer, non-positive S, B, Dn, V, n_docs, n_chunks < V, n_multi
+ * inconsistent with n_chunks), RLT_E_SHAPE (Dn > 16, B*S or Dn + V >= 2^31), RLT_E_ALIGN (weights, gradients, gates, ws off
+ * 16 bytes; indptr / col_ptr off 8; any other array off 4), RLT_E_WORKSPACE.
+ * Plain fp32 (no `precision` argument): a bandwidth kernel.  Algorithmic bytes per pass: 4 KB per nonzero of the batch, plus
+ * the 4 KB x I gradient written once by the backward. */
+#define RLT_SPARSE_CHUNK 256
+typedef struct rlt_sparse_batch {
+    const float* dense; const int32_t* ids; const int32_t* perm;                         /* perm: backward only */
+    const int64_t* indptr; const int32_t* indices; const float* values;                  /* the table, CSR */
+    const int64_t* col_ptr; const int32_t* col_rows; const float* col_vals;              /* backward only: the table by term */
+    const int32_t *chunk_col, *chunk_ptr, *multi_cols;                                   /* backward only */
+    int Dn, n_docs, V, n_chunks, n_multi;
+} rlt_sparse_batch;
+size_t rlt_sparse_inproj_workspace(int S, int B, int Dn, int n_docs, int V, int n_chunks);
+int rlt_sparse_inproj_fwd(const rlt_sparse_batch* sb, int S, int B, const float* wt_fwd, const float* wt_rev,
+                          const float* b_ih_fwd, const float* b_hh_fwd, const float* b_ih_rev, const float* b_hh_rev,
+                          float* gates, void* stream);
+int rlt_sparse_inproj_bwd(const rlt_sparse_batch* sb, int S, int B, const float* dgates, float* dwt_fwd, float* dwt_rev,
+                          float* db_ih_fwd, float* db_hh_fwd, float* db_ih_rev, float* db_hh_rev,
+                          void* ws, size_t ws_bytes, void* stream);
+/* rlt_bilstm_fwd / rlt_bilstm_bwd with layer 0 fed by a sparse batch (models/Bicut.py:10,18 on the input above): layer 0's
+ * gates, dW_ih and biases come from the two entry points above, the recurrences, the stash layout (RLT_OP_BILSTM_STASH) and
+ * layer 1 are those of the dense stack.  w[0].w_ih / g[0].w_ih are the COLUMN-MAJOR (I, 512) buffers.  ws:
+ * rlt_bilstm_sparse_workspace bytes (the dense stack's scratch at 256 inputs + the sparse backward's), 256-byte aligned. */
+size_t rlt_bilstm_sparse_workspace(int S, int B, int Dn, int n_docs, int V, int n_chunks);
+int rlt_bilstm_sparse_fwd(const rlt_sparse_batch* sb, const rlt_lstm_layer_weights* w, int S, int B, float* h_out,
+                          void* stash, size_t stash_bytes, void* ws, size_t ws_bytes, int precision, void* stream);
+int rlt_bilstm_sparse_bwd(const rlt_sparse_batch* sb, const rlt_lstm_layer_weights* w, const float* h_out, const float* dh_out,
+                          int S, int B, void* stash, size_t stash_bytes, const rlt_lstm_layer_grads* g,
+                          void* ws, size_t ws_bytes, int precision, void* stream);
+
 /* ------------------------------------------------------------------ layout helpers
  * (B,S,F) user layout <-> (S*B,F) position-major */
 int rlt_to_position_major(const float* x_bsf, int B, int S, int F, float* x_sbf, void* stream);

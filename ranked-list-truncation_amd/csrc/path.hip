@@ -198,9 +198,14 @@ inline int unpack2(const float* in, size_t n, float* a, float* b, hipStream_t st
     return RLT_LAUNCH_RESULT();
 }
 
+// `sp` != NULL: layer 0 on a sparse batch - the projection comes from rlt_sparse_inproj_fwd (x, I unused)
 int lstm_layer_fwd(const float* x, int I, const rlt_lstm_layer_weights& w, int S, int B, float* gates, float* c, float* h,
-                   const LstmScratch& sc, void* stream) {
+                   const LstmScratch& sc, void* stream, const rlt_sparse_batch* sp = nullptr) {
     const int T = S * B;
+    if (sp) {
+        RLT_TRY(rlt_sparse_inproj_fwd(sp, S, B, w.w_ih[0], w.w_ih[1], w.b_ih[0], w.b_hh[0], w.b_ih[1], w.b_hh[1], gates, stream));
+        return rlt_bilstm_rec_fwd(gates, w.w_hh[0], w.w_hh[1], S, B, h, c, RLT_PRECISION_DEFAULT, stream);
+    }
     if (I <= 3)            // narrow input (layer 0): the projection is formed inside the recurrence
         return rlt_bilstm_rec_fwd_x(x, I, w.w_ih[0], w.b_ih[0], w.b_hh[0], w.w_ih[1], w.b_ih[1], w.b_hh[1], w.w_hh[0], w.w_hh[1],
                                     S, B, gates, h, c, RLT_PRECISION_DEFAULT, stream);
@@ -215,20 +220,27 @@ int lstm_layer_fwd(const float* x, int I, const rlt_lstm_layer_weights& w, int S
 }
 
 // gates <- d(pre-activation gates) in place; weight gradients written (=); dx (T,I) written when not NULL
+// `sp` != NULL: layer 0 on a sparse batch - dW_ih and the bias gradients come from rlt_sparse_inproj_bwd on its own scratch
 int lstm_layer_bwd(const float* x, int I, const rlt_lstm_layer_weights& w, const float* h, float* gates, const float* c,
-                   const float* dh, int S, int B, float* dx, const rlt_lstm_layer_grads& g, const LstmScratch& sc, void* stream) {
+                   const float* dh, int S, int B, float* dx, const rlt_lstm_layer_grads& g, const LstmScratch& sc, void* stream,
+                   const rlt_sparse_batch* sp = nullptr, void* sp_ws = nullptr, size_t sp_ws_bytes = 0) {
     const int T = S * B;
     hipStream_t st = rlt_stream(stream);
     RLT_TRY(rlt_bilstm_rec_bwd(gates, c, w.w_hh[0], w.w_hh[1], dh, S, B, RLT_PRECISION_DEFAULT, stream));
     const float* dA = gates;
-    if (I <= 3) {          // dW_ih of both directions and the bias gradients in ONE streaming pass over dA
+    if (sp) {
+        RLT_TRY(rlt_sparse_inproj_bwd(sp, S, B, dA, g.w_ih[0], g.w_ih[1], g.b_ih[0], g.b_hh[0], g.b_ih[1], g.b_hh[1],
+                                      sp_ws, sp_ws_bytes, stream));
+    } else if (I <= 3) {          // dW_ih of both directions and the bias gradients in ONE streaming pass over dA
         RLT_TRY(rlt_narrow_dw(dA, 1024, x, I, I, T, 1024, sc.dwcat, sc.dbcat, sc.ws, sc.ws_bytes, stream));
     } else {               // both directions in one product; the bias gradient (column sums of dA) rides on it
         RLT_TRY(gemm(1, 0, 1024, I, T, dA, 1024, x, I, sc.dwcat, I, nullptr, 0, sc.dbcat, sc.ws, sc.ws_bytes, stream));
     }
-    RLT_TRY(unpack2(sc.dwcat, (size_t)512 * I, g.w_ih[0], g.w_ih[1], st));
-    RLT_TRY(unpack2(sc.dbcat, 512, g.b_ih[0], g.b_ih[1], st));
-    RLT_TRY(unpack2(sc.dbcat, 512, g.b_hh[0], g.b_hh[1], st));          // d b_hh = d b_ih
+    if (!sp) {
+        RLT_TRY(unpack2(sc.dwcat, (size_t)512 * I, g.w_ih[0], g.w_ih[1], st));
+        RLT_TRY(unpack2(sc.dbcat, 512, g.b_ih[0], g.b_ih[1], st));
+        RLT_TRY(unpack2(sc.dbcat, 512, g.b_hh[0], g.b_hh[1], st));          // d b_hh = d b_ih
+    }
     if (S > 1) {
         const int K = T - B;
         // forward direction: h_{t-1} of position s is the row block of position s-1; reverse: of position s+1
@@ -386,6 +398,45 @@ int rlt_bilstm_bwd(const float* x, int I, const rlt_lstm_layer_weights* w, const
     const LstmScratch k = lstm_scratch(T, I, ws, ws_bytes);
     RLT_TRY(lstm_layer_bwd(s.h0, 256, w[1], h_out, s.gates[1], s.c[1], dh_out, S, B, k.dh0, g[1], k, stream));
     return lstm_layer_bwd(x, I, w[0], s.h0, s.gates[0], s.c[0], k.dh0, S, B, dx, g[0], k, stream);
+}
+
+// ---- the same stack with layer 0 on a sparse batch (csrc/sparse_in.hip): scratch = [ dense stack's at 256 inputs | sparse backward's ]
+size_t rlt_bilstm_sparse_workspace(int S, int B, int Dn, int n_docs, int V, int n_chunks) {
+    const size_t sp = rlt_sparse_inproj_workspace(S, B, Dn, n_docs, V, n_chunks);
+    if (!sp) return 0;
+    return lstm_scratch((size_t)S * B, 256, nullptr).bytes + rup(sp);
+}
+
+int rlt_bilstm_sparse_fwd(const rlt_sparse_batch* sb, const rlt_lstm_layer_weights* w, int S, int B, float* h_out,
+                          void* stash, size_t stash_bytes, void* ws, size_t ws_bytes, int precision, void* stream) {
+    RLT_PREC_SCOPE(precision);
+    RLT_CHECK_ARG(sb && w && h_out && stash && ws && S > 0 && B > 0 && lstm_weights_ok(w[0]) && lstm_weights_ok(w[1]));
+    const size_t T = (size_t)S * B;
+    RLT_CHECK_SHAPE(T <= 0x7fffffffu);
+    if (stash_bytes < lstm_stash(T, nullptr).bytes || ws_bytes < lstm_scratch(T, 256, nullptr).bytes) return RLT_E_WORKSPACE;
+    const LstmStash s = lstm_stash(T, stash, stash_bytes);
+    const LstmScratch k = lstm_scratch(T, 256, ws, ws_bytes);
+    RLT_TRY(lstm_layer_fwd(nullptr, 0, w[0], S, B, s.gates[0], s.c[0], s.h0, k, stream, sb));
+    return lstm_layer_fwd(s.h0, 256, w[1], S, B, s.gates[1], s.c[1], h_out, k, stream);
+}
+
+int rlt_bilstm_sparse_bwd(const rlt_sparse_batch* sb, const rlt_lstm_layer_weights* w, const float* h_out, const float* dh_out,
+                          int S, int B, void* stash, size_t stash_bytes, const rlt_lstm_layer_grads* g,
+                          void* ws, size_t ws_bytes, int precision, void* stream) {
+    RLT_PREC_SCOPE(precision);
+    RLT_CHECK_ARG(sb && w && h_out && dh_out && stash && g && ws && S > 0 && B > 0);
+    RLT_CHECK_ARG(lstm_weights_ok(w[0]) && lstm_weights_ok(w[1]) && lstm_grads_ok(g[0]) && lstm_grads_ok(g[1]));
+    const size_t T = (size_t)S * B;
+    RLT_CHECK_SHAPE(T <= 0x7fffffffu);
+    const size_t sp_bytes = rlt_sparse_inproj_workspace(S, B, sb->Dn, sb->n_docs, sb->V, sb->n_chunks);
+    RLT_CHECK_ARG(sp_bytes > 0);
+    const size_t dense_bytes = lstm_scratch(T, 256, nullptr).bytes;
+    if (stash_bytes < lstm_stash(T, nullptr).bytes || ws_bytes < dense_bytes + rup(sp_bytes)) return RLT_E_WORKSPACE;
+    const LstmStash s = lstm_stash(T, stash, stash_bytes);
+    const LstmScratch k = lstm_scratch(T, 256, ws, dense_bytes);
+    RLT_TRY(lstm_layer_bwd(s.h0, 256, w[1], h_out, s.gates[1], s.c[1], dh_out, S, B, k.dh0, g[1], k, stream));
+    return lstm_layer_bwd(nullptr, 0, w[0], s.h0, s.gates[0], s.c[0], k.dh0, S, B, nullptr, g[0], k, stream,
+                          sb, static_cast<uint8_t*>(ws) + dense_bytes, sp_bytes);
 }
 
 }  // extern "C"

@@ -103,6 +103,13 @@ _SIGNATURES = {
     "rlt_encoder_layer_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_size_t, P, P, P, c_size_t, c_int, P]),
     "rlt_bilstm_fwd": (c_int, [P, c_int, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
     "rlt_bilstm_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, P, c_size_t, P, P, P, c_size_t, c_int, P]),
+    # sparse layer-0 input (BiCut on its bag-of-words input)
+    "rlt_sparse_inproj_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rlt_sparse_inproj_fwd": (c_int, [P, c_int, c_int, P, P, P, P, P, P, P, P]),
+    "rlt_sparse_inproj_bwd": (c_int, [P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
+    "rlt_bilstm_sparse_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "rlt_bilstm_sparse_fwd": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
+    "rlt_bilstm_sparse_bwd": (c_int, [P, P, P, P, c_int, c_int, P, c_size_t, P, P, c_size_t, c_int, P]),
     "rlt_bilstm_generic_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rlt_bilstm_generic_fwd": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
     "rlt_bilstm_generic_bwd": (c_int, [P, c_int, c_int, P, P, P, c_int, c_int, P, c_size_t, P, P, P, c_size_t, c_int, P]),
@@ -120,6 +127,17 @@ class EncoderPtrs(ctypes.Structure):
 class LstmLayerPtrs(ctypes.Structure):
     """rlt_lstm_layer_weights / rlt_lstm_layer_grads: w_ih[2], w_hh[2], b_ih[2], b_hh[2] (0 = forward, 1 = reverse)."""
     _fields_ = [("w_ih", c_void_p * 2), ("w_hh", c_void_p * 2), ("b_ih", c_void_p * 2), ("b_hh", c_void_p * 2)]
+
+
+SPARSE_CHUNK = 256          # RLT_SPARSE_CHUNK
+SPARSE_POINTERS = ("dense", "ids", "perm", "indptr", "indices", "values", "col_ptr", "col_rows", "col_vals",
+                   "chunk_col", "chunk_ptr", "multi_cols")
+SPARSE_INTS = ("Dn", "n_docs", "V", "n_chunks", "n_multi")
+
+
+class SparseBatchPtrs(ctypes.Structure):
+    """rlt_sparse_batch: 12 device pointers in SPARSE_POINTERS order, then the five ints of SPARSE_INTS."""
+    _fields_ = [(f, c_void_p) for f in SPARSE_POINTERS] + [(f, c_int) for f in SPARSE_INTS]
 
 
 def encoder_ptrs(tensors):

@@ -570,6 +570,131 @@ def bilstm(x, params, S, B):
     return BiLSTMFn.apply(x, S, B, *w)
 
 
+# ------------------------------------------------------------------------------ the same stack on a sparse layer-0 input
+class SparseBatch:
+    """BiCut's input without the zeros: `dense` (B,S,Dn) float32 (retrieval score, then the scalar statistics), `ids` (B,S)
+    int32 (the row of each ranked document in `table`) and `table`, an object with `n_docs`, `V`, the CSR arrays `indptr` /
+    `indices` / `values` (int64 / int32 / float32) and the static term index `col_ptr` / `col_rows` / `col_vals` / `chunk_col` /
+    `chunk_ptr` / `multi_cols`, `n_chunks`, `n_multi` on the device of `ids` - dataloader.bicut_data.BowTable.to(device) is one.
+    Densified it would be the reference's (B, S, Dn + V) input.  `validate`: test the ids against the table (the one host
+    synchronisation; leave it out for ids built from the table's own map)."""
+
+    def __init__(self, dense, ids, table, validate=False):
+        if dense.dim() != 3 or dense.dtype != torch.float32 or ids.dim() != 2 or ids.dtype != torch.int32 \
+                or tuple(dense.shape[:2]) != tuple(ids.shape):
+            raise ValueError("SparseBatch: dense must be (B, S, Dn) float32 and ids (B, S) int32 over the same lists")
+        if not 1 <= dense.shape[2] <= 16:
+            raise ValueError(f"SparseBatch: {dense.shape[2]} dense columns; the kernels take 1..16")
+        self.dense, self.ids, self.table, self.validate = dense, ids, table, validate
+
+    @property
+    def shape(self):
+        return (self.ids.shape[0], self.ids.shape[1], self.dense.shape[2] + int(self.table.V))
+
+    def __getitem__(self, lists):
+        if not isinstance(lists, slice):
+            raise TypeError("SparseBatch: index with a slice of lists")
+        return SparseBatch(self.dense[lists], self.ids[lists], self.table, self.validate)
+
+    def to_dense(self):
+        """The reference's (B, S, Dn + V) input (tests and small tables only)."""
+        B, S, Dn = self.dense.shape
+        t = self.table
+        x = torch.zeros((B * S, Dn + int(t.V)), dtype=torch.float32, device=self.ids.device)
+        x[:, :Dn] = self.dense.reshape(B * S, Dn)
+        ids = self.ids.reshape(-1).long()
+        n = (t.indptr[ids + 1] - t.indptr[ids])
+        rows = torch.repeat_interleave(torch.arange(B * S, device=ids.device), n)
+        pos = torch.arange(int(n.sum()), device=ids.device) - torch.repeat_interleave(torch.cumsum(n, 0) - n, n)
+        j = torch.repeat_interleave(t.indptr[ids], n) + pos
+        x[rows, Dn + t.indices[j].long()] = t.values[j]
+        return x.view(B, S, -1)
+
+    def struct(self, perm=None):
+        """rlt_sparse_batch over contiguous arrays; returns (struct, the tensors it points into)."""
+        t = self.table
+        dense = self.dense if self.dense.is_contiguous() else self.dense.contiguous()
+        ids = self.ids if self.ids.is_contiguous() else self.ids.contiguous()
+        N.require_cuda(dense, ids, t.indptr, t.indices, t.values, t.col_ptr, t.col_rows, t.col_vals, t.chunk_col, t.chunk_ptr, t.multi_cols)
+        if t.indptr.dtype != torch.int64 or t.indices.dtype != torch.int32 or t.values.dtype != torch.float32 \
+                or t.indptr.numel() != int(t.n_docs) + 1 or t.col_ptr.dtype != torch.int64 or t.col_ptr.numel() != int(t.V) + 1 \
+                or t.chunk_ptr.numel() != int(t.V) + 1 or t.chunk_col.numel() != int(t.n_chunks):
+            raise ValueError("SparseBatch: the table's arrays must be indptr (n_docs+1) int64, indices int32, values float32 and "
+                             "the term index of dataloader.bicut_data.term_index")
+        if self.validate:
+            lo, hi = torch.aminmax(ids)
+            if int(lo) < 0 or int(hi) >= int(t.n_docs):
+                raise ValueError(f"SparseBatch: document row outside [0, {int(t.n_docs)}): min {int(lo)}, max {int(hi)}")
+        keep = (dense, ids, perm)
+        sb = N.SparseBatchPtrs()
+        for name, a in (("dense", dense), ("ids", ids), ("perm", perm)):
+            setattr(sb, name, None if a is None else a.data_ptr())
+        for name in N.SPARSE_POINTERS[3:]:
+            setattr(sb, name, getattr(t, name).data_ptr())
+        sb.Dn, sb.n_docs, sb.V, sb.n_chunks, sb.n_multi = dense.shape[2], int(t.n_docs), int(t.V), int(t.n_chunks), int(t.n_multi)
+        return sb, keep
+
+
+class BiLSTMSparseFn(Function):
+    """BiLSTMFn with layer 0 fed by a SparseBatch (rlt_bilstm_sparse_fwd / _bwd, csrc/path.hip + csrc/sparse_in.hip): w[0] and
+    w[4] - weight_ih_l0 and weight_ih_l0_reverse - are (512, Dn + V) tensors stored COLUMN-MAJOR (strides (1, 512)), and so are
+    their gradients, of which every column is written.  No gradient for the input: it is data."""
+
+    @staticmethod
+    def forward(ctx, batch, S, B, *w):
+        if len(w) != 16:
+            raise RuntimeError("BiLSTMSparseFn takes the 16 parameters of a 2-layer bidirectional LSTM")
+        I = batch.shape[2]
+        for k in (0, 4):
+            if tuple(w[k].shape) != (512, I) or w[k].stride() != (1, 512):
+                raise RuntimeError(f"sparse BiLSTM: layer-0 input weight of shape {tuple(w[k].shape)} and strides {w[k].stride()}; "
+                                   f"the batch needs (512, {I}) stored column-major, strides (1, 512)")
+        if tuple(batch.ids.shape) != (B, S) or tuple(w[1].shape) != (512, 128) or tuple(w[8].shape) != (512, 256):
+            raise RuntimeError("sparse BiLSTM: hidden size 128, two layers, ids (B, S)")
+        dev = batch.ids.device
+        pr = current_precision()
+        t = batch.table
+        # token rows ordered by (table row, token row): a fixed-size sort, no host synchronisation
+        perm = torch.sort(batch.ids.t().reshape(-1), stable=True)[1].to(torch.int32)
+        sb, keep = batch.struct(perm)
+        stash_bytes = query("rlt_workspace_bytes", N.OP_BILSTM_STASH, S, B, 256, 0, 0, 0, pr)
+        ws_bytes = query("rlt_bilstm_sparse_workspace", S, B, sb.Dn, sb.n_docs, sb.V, sb.n_chunks)
+        if not stash_bytes or not ws_bytes:
+            raise RuntimeError("sparse BiLSTM: shape outside what the kernels support")
+        stash = N.byte_buffer(stash_bytes, dev)
+        ws = N.byte_buffer(ws_bytes, dev)
+        h = torch.empty((S * B, 256), dtype=torch.float32, device=dev)
+        wp = N.lstm_ptrs([w[0:8], w[8:16]])
+        _launch("bilstm_sparse_fwd", lambda: call("rlt_bilstm_sparse_fwd", N.ctypes.byref(sb), wp, S, B, ptr(h), ptr(stash), stash_bytes,
+                                                  ptr(ws), ws_bytes, pr, stream()))
+        ctx.cfg = (S, B, stash_bytes, ws_bytes, pr)
+        ctx.stash, ctx.sb, ctx.keep, ctx.table = stash, sb, keep, t
+        ctx.save_for_backward(h, *w)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        if ctx.stash is None:
+            raise RuntimeError("BiLSTMSparseFn.backward overwrites its stash in place and can run only once")
+        h, *w = ctx.saved_tensors
+        S, B, stash_bytes, ws_bytes, pr = ctx.cfg
+        dh = N.f32c(dh)
+        grads = [torch.empty_like(t) for t in w]            # (preserves the column-major strides of w[0] and w[4])
+        ws = N.byte_buffer(ws_bytes, h.device)
+        wp, gp = N.lstm_ptrs([w[0:8], w[8:16]]), N.lstm_ptrs([grads[0:8], grads[8:16]])
+        _launch("bilstm_sparse_bwd", lambda: call("rlt_bilstm_sparse_bwd", N.ctypes.byref(ctx.sb), wp, ptr(h), ptr(dh), S, B,
+                                                  ptr(ctx.stash), stash_bytes, gp, ptr(ws), ws_bytes, pr, stream()))
+        ctx.stash = None
+        return (None, None, None, *grads)
+
+
+def bilstm_sparse(batch, params, S, B):
+    """`params`: as for bilstm(), with weight_ih_l0 / weight_ih_l0_reverse stored column-major (models.BiCut(sparse_input=True))."""
+    names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+    w = [getattr(params, f"{n}_l{layer}{suffix}") for layer in (0, 1) for suffix in ("", "_reverse") for n in names]
+    return BiLSTMSparseFn.apply(batch, S, B, *w)
+
+
 # ------------------------------------------------------------------------------ layout
 class ToPositionMajorFn(Function):
     """(B,S,F) -> (S*B,F)."""

@@ -25,6 +25,18 @@ from . import native as N
 FORCE_COLLECTIVES = os.environ.get("RLT_FORCE_DIST") == "1"
 
 
+def _flat_view(buf, p):
+    """`buf` (p.numel() elements of a flat bucket) seen with the parameter's OWN shape and strides: a plain view for a contiguous
+    parameter; for a dense permuted one (BiCut's column-major layer-0 input weights) the same permutation over the slot, so that
+    re-pointing the parameter does not silently make it row-major.  Adam is element-wise and does not care."""
+    if p.is_contiguous():
+        return buf.view(p.shape)
+    order = sorted(range(p.dim()), key=lambda i: -p.stride(i))
+    if not p.permute(order).is_contiguous():
+        raise ValueError(f"parameter of shape {tuple(p.shape)} and strides {p.stride()} is not dense: it has no slot in a flat bucket")
+    return buf.as_strided(p.shape, p.stride())
+
+
 class FlatModel:
     def __init__(self, model: torch.nn.Module):
         self.model = model
@@ -44,9 +56,11 @@ class FlatModel:
         with torch.no_grad():
             for p, o in zip(params, offs):
                 n = p.numel()
-                self.flat_param[o:o + n].copy_(p.detach().reshape(-1))
-                p.data = self.flat_param[o:o + n].view(p.shape)
-                p.grad = self.flat_grad[o:o + n].view(p.shape)
+                view = _flat_view(self.flat_param[o:o + n], p)
+                view.copy_(p.detach())
+                grad = _flat_view(self.flat_grad[o:o + n], p)
+                p.data = view
+                p.grad = grad
 
     def zero_grad(self):
         """One memset; keeps the .grad views alive (autograd then accumulates in place)."""

@@ -33,7 +33,7 @@ import torch.distributed as dist
 HERE = os.path.dirname(os.path.abspath(__file__))
 logging.basicConfig(level=logging.INFO)
 
-from dataloader import at_dataloader, cp_dataloader, mc_dataloader, write_synthetic_robust04  # noqa: E402
+from dataloader import at_dataloader, bicut_dataloader, cp_dataloader, mc_dataloader, write_synthetic_robust04  # noqa: E402
 from models import AttnCut, BiCut, Choopy, MMOECut, MOECut, MtAttnCut, MtChoopy, PLECut  # noqa: E402
 from utils import losses  # noqa: E402
 from utils.metrics import Metric  # noqa: E402
@@ -98,8 +98,16 @@ class Trainer:
             loader = mc_dataloader                                             # run.py:87-88: MQ2007 multi-task statistics
         else:
             loader = at_dataloader
-        self.train_loader, self.test_loader, data = loader(args.retrieve_data, args.dataset_name, args.batch_size,
-                                                           device=self.device, base=args.dataset_base, seed=args.seed)
+        # --bicut-stats: BiCut at the width the reference declares it for, on the sparse bag-of-words table (the loader the
+        # reference comments out, run.py:61-63)
+        self.sparse_bicut = name == 'bicut' and bool(getattr(args, "bicut_stats", None))
+        if self.sparse_bicut:
+            self.train_loader, self.test_loader, data = bicut_dataloader(
+                args.retrieve_data, args.dataset_name, args.batch_size, device=self.device, base=args.dataset_base, seed=args.seed,
+                stats=args.bicut_stats, vocab=args.bicut_vocab)
+        else:
+            self.train_loader, self.test_loader, data = loader(args.retrieve_data, args.dataset_name, args.batch_size,
+                                                               device=self.device, base=args.dataset_base, seed=args.seed)
         # the reference hard-codes 3 / 25 / 47 input features and 300 / 40 positions (run.py:34,60,70,86); here both
         # come from the files, and a mismatch with the reference's numbers is reported instead of mis-striding the LSTM
         self.data = data
@@ -113,7 +121,7 @@ class Trainer:
                              f"lengths {data.test_lengths} (only the BiLSTM models bicut / attncut / mtattncut take "
                              "length-bucketed batches)")
         if name == 'bicut':                                                    # run.py:59-64
-            self.model = BiCut(input_size=feat, dropout=args.dropout)
+            self.model = BiCut(input_size=feat, dropout=args.dropout, sparse_input=self.sparse_bicut)
             self.criterion = losses.BiCutLoss(metric=args.criterion)
         elif name == 'choopy':                                                 # run.py:65-68
             self.model = Choopy(seq_len=self.seq_len, dropout=args.dropout)
@@ -341,6 +349,12 @@ def build_parser():
                    help="1: rank 0 first reports the Oracle / Fixed-k / Greedy-k truncation baselines of the run's labels "
                         "(the reference's Baseline/ notebooks), per list length")
     p.add_argument('--fixed-k', type=str, default='5,10,30', help="comma-separated cut positions of the Fixed-k baseline")
+    p.add_argument('--bicut-stats', type=str, default=None,
+                   help="path of the reference's statics/bicut_stats.pkl (dict[doc_id] -> [token count, distinct count, [(term, "
+                        "count), ...]]): --model-name bicut then trains on its bag-of-words input, kept sparse, at input width "
+                        "(dense columns) + (dictionary size); without it bicut reads the three attncut columns as before")
+    p.add_argument('--bicut-vocab', type=int, default=None,
+                   help="dictionary size V of --bicut-stats (the reference: 231448); default 1 + the largest term id of the file")
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Truncation'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

@@ -546,6 +546,119 @@ def features(B=4096, S=300, n_docs=131072, D=200, n_terms=231448, rounds=25):
           f"that column {diff:.2e}; median over {rounds} alternating launches", flush=True)
 
 
+def bicut_sparse(B=20, S=300, V=231448, n_docs=60000, draws=200, rounds=15):
+    """BiCut's layer-0 input projection and its weight gradient on the sparse kernels (rlt_sparse_inproj_fwd / _bwd) at the
+    reference loader's batch of 20 lists x 300 and the published dictionary of 231,448 terms, against the same two products on
+    the dense path (rlt_gemm forward and dW, default precision) on the densified (6000, 231451) input, alternating in one process.
+    The table's profile is ASSUMED (the reference publishes neither figure): 60,000 documents, `draws` term draws per document
+    from a rank^-1 (Zipf) distribution over the dictionary, duplicates merged - about 150 distinct terms per document, the most
+    frequent term in nearly every document -, counts 1..5.  HIP-event time per call, median over `rounds` after warm-up.  Bytes
+    moved, by the header's count: forward 4 KB per nonzero of the batch + the (T, 1024) gates; backward 4 KB per nonzero + the
+    4 KB x I gradient written once; rate against the 6.0 TB/s indexed-row HBM rate.  Then the whole BiCut step (forward,
+    BiCutLoss, backward, FusedAdam over all parameters)."""
+    import numpy as np
+    from dataloader.bicut_data import BowTable
+    from models import BiCut
+    from rlt_hip.parallel import FlatModel, FusedAdam
+    from utils import losses as hl
+    rs = np.random.RandomState(20261016)
+    p = 1.0 / np.arange(1, V + 1)
+    p /= p.sum()
+    key = np.unique(np.repeat(np.arange(n_docs, dtype=np.int64), draws) * V + rs.choice(V, size=n_docs * draws, p=p))
+    rows, indices = key // V, (key % V).astype(np.int32)
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_docs))]).astype(np.int64)
+    table = BowTable.from_csr(indptr, indices, rs.randint(1, 6, size=indices.size).astype(np.float32), V).to(dev)
+    ids_h = rs.randint(0, n_docs, (B, S)).astype(np.int32)
+    nnz = int(np.diff(indptr)[ids_h].sum())
+    T, I, Dn = S * B, 3 + V, 3
+    dense = torch.from_numpy(rs.uniform(0, 4, (B, S, Dn)).astype(np.float32)).to(dev)
+    batch = ops.SparseBatch(dense, torch.from_numpy(ids_h).to(dev), table)
+    perm = torch.sort(batch.ids.t().reshape(-1), stable=True)[1].to(torch.int32)
+    sb, _keep = batch.struct(perm)
+    wt = [torch.randn(I, 512, device=dev) * 0.01 for _ in range(2)]
+    dwt = [torch.empty(I, 512, device=dev) for _ in range(2)]
+    bias = [torch.randn(512, device=dev) * 0.1 for _ in range(4)]
+    db = [torch.empty(512, device=dev) for _ in range(4)]
+    gates = torch.empty(T, 1024, device=dev)
+    dg = torch.randn(T, 1024, device=dev)
+    ws_b = N.query("rlt_sparse_inproj_workspace", S, B, Dn, table.n_docs, V, table.n_chunks)
+    ws = N.byte_buffer(ws_b, dev)
+    import ctypes
+    fwd = lambda: call("rlt_sparse_inproj_fwd", ctypes.byref(sb), S, B, ptr(wt[0]), ptr(wt[1]), ptr(bias[0]), ptr(bias[1]), ptr(bias[2]),
+                       ptr(bias[3]), ptr(gates), stream())
+    bwd = lambda: call("rlt_sparse_inproj_bwd", ctypes.byref(sb), S, B, ptr(dg), ptr(dwt[0]), ptr(dwt[1]), ptr(db[0]), ptr(db[1]),
+                       ptr(db[2]), ptr(db[3]), ptr(ws), ws_b, stream())
+    # the dense path of the same two products: x (T, I) densified, both directions' weights packed (1024, I) as csrc/path.hip does
+    x = batch.to_dense().transpose(0, 1).contiguous().view(T, I)          # position-major rows t = s*B + b
+    wcat = torch.cat([w.t() for w in wt], 0).contiguous()
+    dwcat = torch.empty(1024, I, device=dev)
+    gates_d = torch.empty(T, 1024, device=dev)
+    d_fwd = lambda: ops.gemm(0, 1, T, 1024, I, x, I, wcat, I, gates_d, 1024)
+    d_bwd = lambda: ops.gemm(1, 0, 1024, I, T, dg, 1024, x, I, dwcat, I)
+    t = {"fwd": [], "bwd": [], "dense_fwd": [], "dense_dw": []}
+    fns = (("fwd", fwd), ("bwd", bwd), ("dense_fwd", d_fwd), ("dense_dw", d_bwd))
+    for _ in range(2):
+        for _n, fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for name, fn in fns:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            t[name].append(a.elapsed_time(b) * 1e3)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    by_f, by_b = 4096.0 * nnz + 4096.0 * T, 4096.0 * nnz + 4096.0 * I
+    print(f"bicut_sparse B{B} S{S} V{V} docs{n_docs}: {nnz / T:.1f} terms per ranked document, {nnz} nonzeros in the batch, "
+          f"{table.n_chunks - V} extra chunks over {table.n_multi} terms", flush=True)
+    print(f"    (a) sparse projection forward  {med['fwd']:10.1f} us (min {min(t['fwd']):.1f}, max {max(t['fwd']):.1f}); "
+          f"{by_f / 1e9:.2f} GB -> {by_f / med['fwd'] / 1e6:.2f} TB/s = {by_f / med['fwd'] / 1e6 / 6.0:.2f} of 6.0 TB/s", flush=True)
+    print(f"    (b) sparse weight gradient     {med['bwd']:10.1f} us (min {min(t['bwd']):.1f}, max {max(t['bwd']):.1f}); "
+          f"{by_b / 1e9:.2f} GB -> {by_b / med['bwd'] / 1e6:.2f} TB/s = {by_b / med['bwd'] / 1e6 / 6.0:.2f} of 6.0 TB/s", flush=True)
+    print(f"    (c) dense rlt_gemm forward     {med['dense_fwd']:10.1f} us, dW {med['dense_dw']:10.1f} us "
+          f"({2.0 * T * 1024 * I / med['dense_fwd'] / 1e6:.1f} / {2.0 * T * 1024 * I / med['dense_dw'] / 1e6:.1f} TFLOP/s); "
+          f"(c) / ((a) + (b)) = {(med['dense_fwd'] + med['dense_dw']) / (med['fwd'] + med['bwd']):.1f}; median of {rounds} alternating calls",
+          flush=True)
+    # both paths against float64 products of torch on 64 token rows / 64 weight columns
+    brow = torch.cat([bias[0] + bias[1], bias[2] + bias[3]])[None, :].double()
+    ref_g = x[:64].double() @ wcat.double().t()
+    cols = torch.cat([torch.arange(0, 35, device=dev), torch.randint(0, I, (29,), device=dev)])
+    ref_w = dg.double().t() @ x[:, cols].double()
+    got_w = torch.cat([w.t() for w in dwt], 0)[:, cols].double()
+    print(f"    against float64 on 64 rows / 64 columns: gates sparse {float((gates[:64].double() - brow - ref_g).abs().max()):.2e}, dense "
+          f"{float((gates_d[:64].double() - ref_g).abs().max()):.2e} (max |gate| {float(ref_g.abs().max()):.2f}); dW sparse "
+          f"{float((got_w - ref_w).abs().max()):.2e}, dense {float((dwcat[:, cols].double() - ref_w).abs().max()):.2e} "
+          f"(max |dW| {float(ref_w.abs().max()):.1f})", flush=True)
+    del x, wcat, dwcat, gates_d
+    # the whole step
+    model = BiCut(input_size=I, dropout=0.0, sparse_input=True).to(dev)
+    opt = FusedAdam(FlatModel(model), lr=3e-5, weight_decay=0.005)
+    crit = hl.BiCutLoss(metric="nci")
+    y = (torch.rand(B, S, device=dev) < 0.1).float()
+    model.train()
+
+    def step():
+        opt.zero_grad()
+        crit(model(batch), y).backward()
+        opt.step()
+
+    for _ in range(2):
+        step()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)
+    print(f"    whole BiCut step (forward, BiCutLoss, backward, FusedAdam over {opt.flat.numel / 1e6:.1f} M parameters): "
+          f"{float(np.median(ts)):10.1f} us (min {min(ts):.1f}, max {max(ts):.1f})", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
