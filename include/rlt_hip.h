@@ -195,6 +195,46 @@ int rlt_truncation_curves(const float* labels, int B, int S, double penalty, con
                           double* curves, double* best_f1, int32_t* best_f1_k, double* best_dcg, int32_t* best_dcg_k,
                           double* sums, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ cut report
+ * What a trained model does with every list of a split, and the arithmetic of the reference's `--draw` figure (run.py:188,
+ * 242-298), from one pass over the model's output p and - when there are any - the labels (B,S); S in 1..1024.
+ *   rule   RLT_CUT_ARGMAX: p is (B,S), k = first maximum + 1 (run.py:141-142);
+ *          RLT_CUT_PAIR:   p is (B,S,2), BiCut's rule (run.py:131-136): k = S when no position prefers class 0, otherwise the
+ *                          first such position + 1; a tie goes to class 0; p 8-byte aligned.
+ *   labels NULL = label-free mode: only k, p_k, margin, hist, pred_curve and sums[4] are produced (every labelled output must
+ *          then be NULL; metric, penalty, metric_penalty, tau, dcg_coef and dcg_table are not read).
+ * Per-list outputs (B each, each may be NULL):
+ *   k int32; p_k fp32 = the winning value (PAIR: the class-0 value at position k - 1); margin fp32 = the maximum minus the
+ *   runner-up, 0 for S = 1 (PAIR: class 0 minus class 1 at position k - 1, negative when no position prefers class 0);
+ *   f1, dcg float64 = F1@k and DCG@k (DCG with metric_penalty), bit-identical to rlt_cut_metrics_ex;
+ *   best_f1, best_f1_k, best_dcg, best_dcg_k = the list's best over k = 0..S and its first maximum, bit-identical to
+ *   rlt_truncation_curves with penalty = metric_penalty;
+ *   better int32 = the number of cut positions 1..S whose reward is strictly greater than the reward at k, the reward r
+ *   being bit for bit the fp32 one of rlt_reward_matrix_ex(labels, dcg_coef, metric, penalty) (dcg_coef: fp32 log2(j + 2),
+ *   S entries, required for RLT_METRIC_DCG).
+ * Split outputs (float64, 8-byte aligned, each may be NULL; accumulate = 1 ADDS this batch, 0 overwrites):
+ *   hist (S+1) = counts of k;  pred_curve (S) = sum over lists of softmax_j(p_j / sharpen) (PAIR: of the class-0 column);
+ *   reward_curve (S) = sum over lists of softmax_j(r_j / tau);  sums (5) = sum f1, sum dcg (both in rlt_cut_metrics_ex's own
+ *   order: bit-identical to its sums), sum best_f1, sum best_dcg, number of lists.
+ * Both softmaxes subtract the row maximum and are formed in float64 (tau, sharpen > 0; the reference draws tau = 0.9 and
+ * sharpen = tau * 1e-3).  The reference computes exp(p / 9e-4) in fp32 with no subtraction: it overflows once a p exceeds about
+ * 0.08 and the figure is NaN from there; where the reference is finite this pass agrees with it to the reference's own fp32
+ * rounding, and it stays finite everywhere else.  The `norm_s[-3:] = norm_s[-4]` overwrite of run.py:283 is presentation and
+ * not applied here.
+ * dcg_table: as for rlt_loss_metrics.  ws: rlt_cut_report_workspace(B, S) bytes, 8-byte aligned (0 for B <= 0 or S outside
+ * 1..1024): one float64 record per workgroup, and F1@k / DCG@k per list for the ordered sums.  Three launches (two without
+ * labels or sums): the pass (a wavefront owns whole lists - four per wavefront at S <= 64 - with its per-position sums in
+ * registers), a fixed-order column reduction of the records, and the ordered sums; no atomics, no allocation, no host
+ * synchronisation, bitwise reproducible.  Algorithmic bytes per list: 8 S read (4 S without labels). */
+#define RLT_CUT_ARGMAX 0
+#define RLT_CUT_PAIR   1
+size_t rlt_cut_report_workspace(int B, int S);
+int rlt_cut_report(const float* p, int rule, const float* labels, const float* dcg_coef, int B, int S, int metric, float penalty,
+                   double metric_penalty, double tau, double sharpen, const void* dcg_table, int accumulate,
+                   int32_t* k, float* p_k, float* margin, double* f1, double* dcg, double* best_f1, int32_t* best_f1_k,
+                   double* best_dcg, int32_t* best_dcg_k, int32_t* better, double* hist, double* pred_curve, double* reward_curve,
+                   double* sums, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ dense contraction (M2-M7)
  * C[M,N] (+)= op(A) * op(B) (+ bias[N] + bias2[N]), optional ReLU.  fp32 in, fp32 accumulate on
  * the f32 MFMA (exact fp32 products, v_mfma_f32_32x32x2_f32).

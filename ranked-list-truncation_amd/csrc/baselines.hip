@@ -28,28 +28,6 @@ constexpr int CURVES_MAX_GRID = 1024;   // workgroups (4 per CU); beyond that th
 
 __host__ __device__ constexpr int curves_cols(int S) { return 3 * S + 2; }   // record: F1, DCG, c sums for k = 1..S, sum best F1, sum best DCG
 
-// inclusive scan over each group of L lanes (L = 64: the wavefront; L = 16: its rows), identity `id` for lanes without a source
-template <int L, typename T, typename Op>
-__device__ __forceinline__ T group_scan(T v, T id, Op op) {
-    v = op(v, rlt_dpp<0x111, 0xf>(id, v));      // row_shr:1
-    v = op(v, rlt_dpp<0x112, 0xf>(id, v));      // row_shr:2
-    v = op(v, rlt_dpp<0x114, 0xf>(id, v));      // row_shr:4
-    v = op(v, rlt_dpp<0x118, 0xf>(id, v));      // row_shr:8   -> inclusive inside each row of 16
-    if constexpr (L == 64) {
-        v = op(v, rlt_dpp<0x142, 0xa>(id, v));  // row_bcast:15
-        v = op(v, rlt_dpp<0x143, 0xc>(id, v));  // row_bcast:31
-    }
-    return v;
-}
-// the value of the group's last lane in every lane of the group
-template <int L, typename T>
-__device__ __forceinline__ T group_last(T v, int lane) {
-    if constexpr (L == 64) return rlt_readlane(v, 63);
-    else return __shfl(v, lane | (L - 1));
-}
-template <int L, typename T, typename Op>
-__device__ __forceinline__ T group_reduce(T v, T id, Op op, int lane) { return group_last<L>(group_scan<L>(v, id, op), lane); }
-
 struct CurvesArgs {
     const float* y;         // (B, S) labels
     const double* tab;      // DCG table: [j] = 1 / log2(j + 2)
@@ -91,7 +69,7 @@ __global__ __launch_bounds__(256) void truncation_curves_kernel(CurvesArgs a) {
             yv[r] = (live && j < S) ? row[j] : 0.f;
             n_lane += (double)yv[r];
         }
-        const double N = group_reduce<L>(n_lane, 0.0, add, lane);          // hits in the list
+        const double N = rlt_group_reduce<L>(n_lane, 0.0, add, lane);          // hits in the list
         double c_carry = 0.0, d_carry = 0.0;
         double bf = 0.0, bd = 0.0;              // k = 0: value 0
         int kf = 0, kd = 0;
@@ -100,12 +78,12 @@ __global__ __launch_bounds__(256) void truncation_curves_kernel(CurvesArgs a) {
             const int j = r * L + l;
             const bool valid = live && j < S;
             const double gain = valid ? ((yv[r] == 1.f) ? 1.0 : a.penalty) * coef[r] : 0.0;
-            const double ci = group_scan<L>((double)yv[r], 0.0, add);
-            const double di = group_scan<L>(gain, 0.0, add);
+            const double ci = rlt_group_scan<L>((double)yv[r], 0.0, add);
+            const double di = rlt_group_scan<L>(gain, 0.0, add);
             const double c = c_carry + ci, dcg = d_carry + di;
             if (r + 1 < R) {
-                c_carry += group_last<L>(ci, lane);
-                d_carry += group_last<L>(di, lane);
+                c_carry += rlt_group_last<L>(ci, lane);
+                d_carry += rlt_group_last<L>(di, lane);
             }
             // cal_F1, operation for operation
             const double p = c / (double)(j + 1);
@@ -123,9 +101,9 @@ __global__ __launch_bounds__(256) void truncation_curves_kernel(CurvesArgs a) {
         // rose above 0 holds k = 0)
         const auto mx = [](double x, double z) { return x > z ? x : z; };
         const auto mn = [](int x, int z) { return x < z ? x : z; };
-        const double mf = group_reduce<L>(bf, 0.0, mx, lane), md = group_reduce<L>(bd, 0.0, mx, lane);
-        const int kfm = group_reduce<L>(bf == mf ? kf : 0x7fffffff, 0x7fffffff, mn, lane);
-        const int kdm = group_reduce<L>(bd == md ? kd : 0x7fffffff, 0x7fffffff, mn, lane);
+        const double mf = rlt_group_reduce<L>(bf, 0.0, mx, lane), md = rlt_group_reduce<L>(bd, 0.0, mx, lane);
+        const int kfm = rlt_group_reduce<L>(bf == mf ? kf : 0x7fffffff, 0x7fffffff, mn, lane);
+        const int kdm = rlt_group_reduce<L>(bd == md ? kd : 0x7fffffff, 0x7fffffff, mn, lane);
         if (live && l == 0) {
             if (a.best_f1) a.best_f1[b] = mf;
             if (a.best_f1_k) a.best_f1_k[b] = kfm;

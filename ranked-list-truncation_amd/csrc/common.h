@@ -98,6 +98,29 @@ __device__ __forceinline__ T wave_scan_op(T v, T id, Op op) {
     v = op(v, rlt_dpp<0x143, 0xc>(id, v));      // row_bcast:31 into rows 2 and 3
     return v;
 }
+// the same scan over each group of L lanes (L = 64: the wavefront, wave_scan_op itself; L = 16: each row of 16 lanes on its own - four
+// lists per wavefront in the per-list scans of baselines.hip and report.hip), the value of a group's last lane in every lane of
+// the group, and the reduction they make together.  One definition: the bit-for-bit contracts between those kernels rest on it.
+template <int L, typename T, typename Op>
+__device__ __forceinline__ T rlt_group_scan(T v, T id, Op op) {
+    static_assert(L == 16 || L == 64, "rows of 16 lanes or the whole wavefront");
+    v = op(v, rlt_dpp<0x111, 0xf>(id, v));      // row_shr:1
+    v = op(v, rlt_dpp<0x112, 0xf>(id, v));      // row_shr:2
+    v = op(v, rlt_dpp<0x114, 0xf>(id, v));      // row_shr:4
+    v = op(v, rlt_dpp<0x118, 0xf>(id, v));      // row_shr:8   -> inclusive inside each row of 16
+    if constexpr (L == 64) {
+        v = op(v, rlt_dpp<0x142, 0xa>(id, v));  // row_bcast:15
+        v = op(v, rlt_dpp<0x143, 0xc>(id, v));  // row_bcast:31
+    }
+    return v;
+}
+template <int L, typename T>
+__device__ __forceinline__ T rlt_group_last(T v, int lane) {
+    if constexpr (L == 64) return rlt_readlane(v, 63);
+    else return __shfl(v, lane | (L - 1));
+}
+template <int L, typename T, typename Op>
+__device__ __forceinline__ T rlt_group_reduce(T v, T id, Op op, int lane) { return rlt_group_last<L>(rlt_group_scan<L>(v, id, op), lane); }
 // sum over the 64 lanes, the same value (a scalar register) in every lane; fixed order
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

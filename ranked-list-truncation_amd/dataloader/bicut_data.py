@@ -167,7 +167,7 @@ class BicutData(rank_data.RankData):
         if stats is None:
             raise ValueError("BicutData: give the path of bicut_stats.pkl (stats=...)")
         base = os.path.join(base or rank_data.DATASET_BASE, retrieve_data)
-        gt = rank_data._load(os.path.join(base, "gt.pkl"))
+        gt = rank_data._load_gt(base)
         raws = {split: rank_data._load(os.path.join(base, f"{dataset_name}_{split}.pkl")) for split in ("train", "test")}
         self.table = stats if isinstance(stats, BowTable) else BowTable.from_pickle(stats, raws["train"], raws["test"], vocab=vocab)
         self.buckets = {split: {s: (rank_data._pin(torch.from_numpy(x)), rank_data._pin(torch.from_numpy(y)), qids)

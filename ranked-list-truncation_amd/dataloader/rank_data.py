@@ -22,6 +22,7 @@ pinned staging buffers and one async H2D copy on a side stream, one batch ahead 
 Under torch.distributed every rank draws the SAME permutations (one seed broadcast from rank 0), so
 that rank r's shard of a batch (rlt_hip.parallel.shard_bounds) is a true partition of that batch.
 """
+import contextlib
 import os
 import pickle
 
@@ -36,6 +37,29 @@ DATASET_BASE = os.environ.get("RLT_DATASET_BASE", os.path.join(os.path.dirname(o
 def _load(path):
     with open(path, "rb") as f:
         return pickle.load(f)
+
+
+_LABELS_OPTIONAL = False
+
+
+@contextlib.contextmanager
+def labels_optional(flag=True):
+    """Within this context a data directory may lack gt.pkl: every label is then 0.  For a label-free report of lists nobody
+    has judged (run.py --epochs 0 --report-out PATH --report-labels 0); a gt.pkl that exists is read as usual.  (A context, not
+    an argument: the loaders keep the reference's signatures.)"""
+    global _LABELS_OPTIONAL
+    saved, _LABELS_OPTIONAL = _LABELS_OPTIONAL, bool(flag)
+    try:
+        yield
+    finally:
+        _LABELS_OPTIONAL = saved
+
+
+def _load_gt(base):
+    path = os.path.join(base, "gt.pkl")
+    if _LABELS_OPTIONAL and not os.path.exists(path):
+        return {}
+    return _load(path)
 
 
 def _pack(raw, stats, gt):
@@ -75,7 +99,7 @@ class RankData:
     def __init__(self, retrieve_data="robust04", dataset_name="bm25", with_stats=True, base=None, stats_dir="attncut",
                  doc_table=None):
         base = os.path.join(base or DATASET_BASE, retrieve_data)
-        gt = _load(os.path.join(base, "gt.pkl"))
+        gt = _load_gt(base)
         self.buckets = {}
         for split in ("train", "test"):
             raw = _load(os.path.join(base, f"{dataset_name}_{split}.pkl"))

@@ -6,7 +6,7 @@ from rlt_hip import ops
 from . import _common as C
 
 
-class AttnCut(nn.Module):
+class AttnCut(C.CutModel):
     """BiLSTM(2 layers, H=128) -> encoder layer(s) with list-axis attention -> Linear -> softmax over
     positions.  Same constructor, state_dict keys and output shape (B,S,1) as the reference."""
 

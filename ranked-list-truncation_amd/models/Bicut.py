@@ -15,7 +15,7 @@ from rlt_hip import ops
 from . import _common as C
 
 
-class BiCut(nn.Module):
+class BiCut(C.CutModel):
     def __init__(self, input_size=231449, lstm_hiden_size=128, lstm_layers=2, fc_dimensions=256, dropout=0.4, sparse_input=False):
         super().__init__()
         if lstm_hiden_size != 128 or lstm_layers != 2:

@@ -7,7 +7,7 @@ from rlt_hip import ops
 from . import _common as C
 
 
-class Choopy(nn.Module):
+class Choopy(C.CutModel):
     def __init__(self, seq_len: int = 300, d_model: int = 128, n_head: int = 8, num_layers: int = 3, dropout=0.2):
         super().__init__()
         self.seq_len, self.n_head, self.dropout = seq_len, n_head, dropout

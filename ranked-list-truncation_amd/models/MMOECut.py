@@ -49,7 +49,7 @@ class TowerRerank(_Tower):
         super().__init__(d_model, "rerank_layer")
 
 
-class MMOECut(nn.Module):
+class MMOECut(C.CutModel):
     def __init__(self, seq_len: int = 300, num_experts=3, num_tasks=3, input_size=3, encoding_size=128,
                  d_model=256, n_head=4, num_layers=1, dropout=0.2):
         super().__init__()

@@ -6,7 +6,7 @@ from . import _common as C
 from ._mt import mt_heads
 
 
-class MtAttnCut(nn.Module):
+class MtAttnCut(C.CutModel):
     def __init__(self, input_size: int = 3, d_model: int = 256, n_head: int = 4, num_layers: int = 1,
                  num_tasks: float = 3, dropout: float = 0.4):
         super().__init__()

@@ -7,7 +7,7 @@ from . import _common as C
 from ._mt import mt_heads
 
 
-class MtChoopy(nn.Module):
+class MtChoopy(C.CutModel):
     def __init__(self, seq_len: int = 300, d_model: int = 128, n_head: int = 8, num_layers: int = 3,
                  num_tasks: float = 3, dropout: float = 0.4):
         super().__init__()

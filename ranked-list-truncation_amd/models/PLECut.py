@@ -8,7 +8,7 @@ from . import _common as C
 from .MMOECut import Expert, TowerClass, TowerCut, TowerRerank
 
 
-class PLECut(nn.Module):
+class PLECut(C.CutModel):
     def __init__(self, seq_len: int = 300, num_experts=3, input_size=3, encoding_size=128, d_model=256, n_head=2,
                  num_layers=1, dropout=0.1):
         super().__init__()

@@ -83,3 +83,22 @@ def pick_tasks(num_tasks):
     if num_tasks == 2.1:
         return ["classi", "decison_layer"]
     return ["rerank", "decison_layer"]
+
+
+class CutModel(nn.Module):
+    """Common base of the truncation models: `truncate` says where the model cuts each list, with no labels."""
+
+    def truncate(self, x):
+        """x: what forward takes (BiCut with sparse_input: an ops.SparseBatch).  Runs the model in eval mode under no_grad and
+        returns (k (B,) int32, p_k (B,) float32) on the device: each list's cut and the winning value (rlt_cut_report, label-free:
+        first maximum + 1, or BiCut's rule on its (B,S,2) output).  The module's train / eval state is restored."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = self(x)
+                cut = out[-1] if isinstance(out, (list, tuple)) else out
+                per, _ = ops.cut_report(cut)
+        finally:
+            self.train(was_training)
+        return per["k"], per["p_k"]

@@ -19,6 +19,7 @@ LOSS_EXPECT, LOSS_CE, LOSS_KL, LOSS_JS = 0, 1, 2, 3
 GEMM_RELU, GEMM_ACCUMULATE = 1, 2
 HEAD_SOFTMAX, HEAD_SIGMOID, HEAD_IDENTITY = 0, 1, 2
 PROBE_BCE, PROBE_RERANK = 0, 1
+CUT_ARGMAX, CUT_PAIR = 0, 1
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
 
@@ -48,6 +49,9 @@ _SIGNATURES = {
     "rlt_task_metrics": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "rlt_truncation_curves_workspace": (c_size_t, [c_int, c_int]),
     "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "rlt_cut_report_workspace": (c_size_t, [c_int, c_int]),
+    "rlt_cut_report": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_float, c_double, c_double, c_double, P, c_int,
+                               P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_probe_heads_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rlt_probe_heads": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
     "rlt_neighbor_features": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_int, c_int, P]),

@@ -1162,6 +1162,56 @@ def truncation_curves(labels, penalty=-1.0, curves=None, sums=None, per_list=Fal
     return curves, sums, best
 
 
+CUT_REPORT_PER_LIST = ("k", "p_k", "margin")
+CUT_REPORT_LABELLED = ("f1", "dcg", "best_f1", "best_f1_k", "best_dcg", "best_dcg_k", "better")
+_CUT_REPORT_DTYPES = {"k": torch.int32, "p_k": torch.float32, "margin": torch.float32, "f1": torch.float64, "dcg": torch.float64,
+                      "best_f1": torch.float64, "best_f1_k": torch.int32, "best_dcg": torch.float64, "best_dcg_k": torch.int32,
+                      "better": torch.int32}
+
+
+def cut_report(p, labels=None, metric=N.METRIC_F1, penalty=-1.0, metric_penalty=-1.0, tau=0.9, sharpen=None, acc=None,
+               per_list=True):
+    """One pass over a model's output and (optionally) the labels (rlt_cut_report).  p: the cut distribution (B,S) / (B,S,1), or
+    BiCut's (B,S,2) (the PAIR rule); labels (B,S) or None for label-free mode.  Returns (per-list dict, acc): the dict holds k,
+    p_k, margin and, with labels, f1, dcg, best_f1, best_f1_k, best_dcg, best_dcg_k, better (empty with per_list=False); acc is
+    the dict of split sums hist (S+1), pred_curve (S), reward_curve (S), sums (5) in float64 - pass the dict of an earlier call
+    back as `acc` and this batch is ADDED into it.  sharpen defaults to the reference's tau * 1e-3.  No host synchronisation."""
+    p = N.f32c(p.detach())
+    N.require_cuda(p, labels)
+    if p.dim() == 3 and p.shape[2] == 1:
+        p = p.reshape(p.shape[0], p.shape[1])
+    rule = N.CUT_PAIR if p.dim() == 3 and p.shape[2] == 2 else N.CUT_ARGMAX
+    if p.dim() != (3 if rule == N.CUT_PAIR else 2):
+        raise ValueError(f"cut_report: the output must be (B,S), (B,S,1) or (B,S,2); got {tuple(p.shape)}")
+    B, S = p.shape[:2]
+    dev = p.device
+    if labels is not None:
+        labels = N.f32c(labels)
+        if tuple(labels.shape) != (B, S):
+            raise ValueError(f"cut_report: labels {tuple(labels.shape)} do not match the output's {(B, S)}")
+    sharpen = float(tau) * 1e-3 if sharpen is None else float(sharpen)
+    accumulate = acc is not None
+    if not accumulate:
+        acc = {"hist": torch.zeros((S + 1,), dtype=torch.float64, device=dev),
+               "pred_curve": torch.zeros((S,), dtype=torch.float64, device=dev),
+               "reward_curve": torch.zeros((S,), dtype=torch.float64, device=dev),
+               "sums": torch.zeros((5,), dtype=torch.float64, device=dev)}
+    elif acc["pred_curve"].numel() != S:
+        raise ValueError(f"cut_report: lists of {S} positions, the accumulator holds {acc['pred_curve'].numel()}")
+    names = () if not per_list else CUT_REPORT_PER_LIST + (CUT_REPORT_LABELLED if labels is not None else ())
+    out = {n: torch.empty((B,), dtype=_CUT_REPORT_DTYPES[n], device=dev) for n in names}
+    o = lambda n: ptr(out.get(n))
+    coef = dcg_coef(S, dev) if labels is not None and metric == N.METRIC_DCG else None
+    ws_bytes = query("rlt_cut_report_workspace", B, S)
+    ws = workspace(ws_bytes, dev)
+    call("rlt_cut_report", ptr(p), rule, ptr(labels), ptr(coef), B, S, int(metric), float(penalty), float(metric_penalty),
+         float(tau), sharpen, ptr(dcg_table(dev)) if labels is not None else None, int(accumulate),
+         o("k"), o("p_k"), o("margin"), o("f1"), o("dcg"), o("best_f1"), o("best_f1_k"), o("best_dcg"), o("best_dcg_k"), o("better"),
+         ptr(acc["hist"]), ptr(acc["pred_curve"]), ptr(acc["reward_curve"]) if labels is not None else None, ptr(acc["sums"]),
+         ptr(ws), ws_bytes, stream())
+    return out, acc
+
+
 def neighbor_features(doc_ids, table, out=None, col=0, validate=True):
     """AttnCut's neighbour-similarity statistics (rlt_neighbor_features): doc_ids (B,S) int32 rows of `table` in rank order ->
     per position the cosine similarity to the neighbouring documents, the tf-idf column first, then the doc2vec one.

@@ -17,7 +17,13 @@ state_dict checkpoint on best test F1, run.py:153-232) and the same log lines.  
     `<tensorboard-dir>/scalars.jsonl` (and to a SummaryWriter when tensorboard is installed);
   * --baselines 1: rank 0 first reports the truncation baselines of the reference's Baseline/ notebooks (Oracle, Fixed-k,
     Greedy-k) on the run's own labels, per list length, on the device (utils/baselines.py);
-  * not carried over: matplotlib plots and the hyper-parameter random search.
+  * --report-out PATH: rank 0 runs a split through the trained (or loaded: --epochs 0 --ft 1 --model-path CKPT) model and writes
+    what it does per query - cut, winning value, margin, F1 / DCG at the cut, the list's best, the count of better cuts - with
+    the k histogram, the summary and the two curves below per list length, from one fused pass per batch (utils/report.py);
+  * --draw 1: the arithmetic of the reference's figure (run.py:188,242-298) - the batch-mean softmax of the reward and the
+    batch-mean sharpened softmax of the model's output - goes to scalars.jsonl under draw/reward and draw/prediction on the
+    reference's condition (even epoch, a batch of more than 40 lists); no image is written;
+  * not carried over: rendering figures and the hyper-parameter random search.
 """
 import argparse
 import configparser
@@ -63,6 +69,11 @@ class ScalarLog:
         if self.tb is not None:
             self.tb.add_scalar(tag, value, step)
 
+    def add_curve(self, tag, values, step):
+        """A whole curve under one tag (the --draw curves): one JSON line with `values`; not mirrored to tensorboard."""
+        if self.file is not None:
+            self.file.write(json.dumps({"tag": tag, "values": [float(v) for v in values], "step": int(step)}) + "\n")
+
     def close(self):
         if self.file is not None:
             self.file.close()
@@ -101,13 +112,17 @@ class Trainer:
         # --bicut-stats: BiCut at the width the reference declares it for, on the sparse bag-of-words table (the loader the
         # reference comments out, run.py:61-63)
         self.sparse_bicut = name == 'bicut' and bool(getattr(args, "bicut_stats", None))
-        if self.sparse_bicut:
-            self.train_loader, self.test_loader, data = bicut_dataloader(
-                args.retrieve_data, args.dataset_name, args.batch_size, device=self.device, base=args.dataset_base, seed=args.seed,
-                stats=args.bicut_stats, vocab=args.bicut_vocab)
-        else:
-            self.train_loader, self.test_loader, data = loader(args.retrieve_data, args.dataset_name, args.batch_size,
-                                                               device=self.device, base=args.dataset_base, seed=args.seed)
+        # a label-free report of a loaded model (--epochs 0 --report-out --report-labels 0) reads no label: gt.pkl may be missing
+        need_labels = not (getattr(args, "report_out", None) and not getattr(args, "report_labels", 1) and args.epochs == 0)
+        from dataloader import rank_data
+        with rank_data.labels_optional(not need_labels):
+            if self.sparse_bicut:
+                self.train_loader, self.test_loader, data = bicut_dataloader(
+                    args.retrieve_data, args.dataset_name, args.batch_size, device=self.device, base=args.dataset_base, seed=args.seed,
+                    stats=args.bicut_stats, vocab=args.bicut_vocab)
+            else:
+                self.train_loader, self.test_loader, data = loader(args.retrieve_data, args.dataset_name, args.batch_size,
+                                                                   device=self.device, base=args.dataset_base, seed=args.seed)
         # the reference hard-codes 3 / 25 / 47 input features and 300 / 40 positions (run.py:34,60,70,86); here both
         # come from the files, and a mismatch with the reference's numbers is reported instead of mis-striding the LSTM
         self.data = data
@@ -296,6 +311,71 @@ class Trainer:
             out[str(L)] = rec
         return out
 
+    def _split_batches(self, split):
+        """(length, qids, x, y) of every bucket of a split in file order (no shuffling); BicutData keeps the same buckets."""
+        for L, (x, y, qids) in sorted(self.data.buckets[split].items()):
+            yield L, qids, x, y
+
+    def _forward_eval(self, x):
+        """The cut distribution of one batch of a bucket, eval mode, no gradient (sparse BiCut: as SparseBatchLoader feeds it)."""
+        x = x.to(self.device, non_blocking=True)
+        if self.sparse_bicut:
+            Dn = self.data.table.Dn
+            x = ops.SparseBatch(x[..., :Dn].contiguous(), x[..., Dn].contiguous().view(torch.int32), self.data.table)
+        self.model.eval()
+        with torch.no_grad():
+            out = self.model(x)
+        return out[-1] if isinstance(out, (list, tuple)) else out
+
+    def report(self, path, split="test", labelled=True):
+        """--report-out: every list of `split`, length bucket by length bucket, through the model and `CutReport`; one .npz with
+        the per-query arrays (rows in the order of `qid`), and per list length the k histogram, the two curves and the summary
+        (JSON).  Returns {length: summary}.  No collective: rank 0 calls it.  The model runs once per batch and `CutReport` takes
+        k and p_k from that output in the same pass as the rest - what `model.truncate` returns for the batch, without the
+        second forward pass a call of it would cost."""
+        import numpy as np
+        from utils.report import CutReport
+        arrays, summaries, per_len = {}, {}, {}
+        qid_all, len_all = [], []
+        for L, qids, x, y in self._split_batches(split):
+            rep = CutReport(L, metric=self.args.criterion, device=self.device)
+            for i in range(0, x.shape[0], self.batch_size):
+                cut = self._forward_eval(x[i:i + self.batch_size])
+                rep.update(cut, y[i:i + self.batch_size] if labelled else None)
+            for name, a in rep.per_query().items():
+                arrays.setdefault(name, []).append(a)
+            qid_all += [str(q) for q in qids]
+            len_all += [L] * len(qids)
+            reward, pred = rep.curves(tail_fix=True)
+            summ = rep.summary()
+            per_len[f"hist_{L}"] = np.asarray(summ.pop("hist"))
+            per_len[f"pred_curve_{L}"] = pred
+            if reward is not None:
+                per_len[f"reward_curve_{L}"] = reward
+            summaries[str(L)] = summ
+            logging.info('\tReport ({} split, S = {}): {}'.format(split, L, json.dumps(summ)))
+            for key, v in summ.items():
+                self.writer.add_scalar('report/{}'.format(key), v, L)
+        np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
+                 summary=np.asarray(json.dumps(summaries)), **{k: np.concatenate(v) for k, v in arrays.items()}, **per_len)
+        return summaries
+
+    def draw(self, epoch):
+        """--draw 1 (run.py:188): for every test batch of more than 40 lists, the two curves `Trainer.plot` draws (run.py:262-283,
+        tau = 0.9) into the scalar log.  The batches are the test buckets in file order."""
+        from utils.report import CutReport
+        step = 0
+        for L, _qids, x, y in self._split_batches("test"):
+            for i in range(0, x.shape[0], self.batch_size):
+                if x[i:i + self.batch_size].shape[0] <= 40:
+                    continue
+                rep = CutReport(L, metric=self.args.criterion, tau=0.9, device=self.device)
+                rep.update(self._forward_eval(x[i:i + self.batch_size]), y[i:i + self.batch_size])
+                reward, pred = rep.curves(tail_fix=False)      # the figure's norm_s[-3:] overwrite is presentation: not logged
+                self.writer.add_curve('draw/reward', reward, epoch * 100000 + step)
+                self.writer.add_curve('draw/prediction', pred, epoch * 100000 + step)
+                step += 1
+
     def run(self):
         if self.args.baselines and self.rank == 0:
             self.baseline_results = self.baselines()
@@ -304,6 +384,11 @@ class Trainer:
         for epoch in range(self.epochs):
             self.train_epoch(epoch)
             self.test(epoch)
+            if getattr(self.args, "draw", 0) and epoch % 2 == 0 and self.rank == 0:      # (drivers build their own Namespace)
+                self.draw(epoch)
+        if getattr(self.args, "report_out", None) and self.rank == 0:
+            self.report_results = self.report(self.args.report_out, getattr(self.args, "report_split", "test"),
+                                              bool(getattr(self.args, "report_labels", 1)))
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -349,6 +434,15 @@ def build_parser():
                    help="1: rank 0 first reports the Oracle / Fixed-k / Greedy-k truncation baselines of the run's labels "
                         "(the reference's Baseline/ notebooks), per list length")
     p.add_argument('--fixed-k', type=str, default='5,10,30', help="comma-separated cut positions of the Fixed-k baseline")
+    p.add_argument('--report-out', type=str, default=None,
+                   help="rank 0 writes a per-query cut report of the final model (.npz: k, winning value, margin, F1 / DCG at the cut, "
+                        "each list's best and the count of better cuts, keyed by query id; per list length the k histogram, the "
+                        "reward / prediction curves and the summary); with --epochs 0 --ft 1 --model-path CKPT it reports a checkpoint")
+    p.add_argument('--report-split', type=str, default='test', choices=('train', 'test'))
+    p.add_argument('--report-labels', type=int, default=1, choices=(0, 1), help="0: label-free report (k, winning value, margin only)")
+    p.add_argument('--draw', type=int, default=0, choices=(0, 1),
+                   help="1: on even epochs, the reward and prediction curves of the reference's figure for every test batch of more "
+                        "than 40 lists go to scalars.jsonl (draw/reward, draw/prediction); no image is written")
     p.add_argument('--bicut-stats', type=str, default=None,
                    help="path of the reference's statics/bicut_stats.pkl (dict[doc_id] -> [token count, distinct count, [(term, "
                         "count), ...]]): --model-name bicut then trains on its bag-of-words input, kept sparse, at input width "

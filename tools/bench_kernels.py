@@ -166,6 +166,64 @@ def baselines(B=1048576, S=300):
           f"(records {wsb / 1e6:.1f} MB)", flush=True)
 
 
+def report(B=1048576, S=300, reps=9):
+    """rlt_cut_report (the fused per-query report + the --draw curves) against the composition it replaces on the same data:
+    rlt_cut_metrics_ex + rlt_truncation_curves + rlt_reward_matrix_ex (r written) + torch softmax / sum over r / tau and over
+    p / sharpen in float64.  1,048,576 lists x 300 positions, the shape of the `baselines` bench.  HIP events around single
+    alternating launches, the median of `reps`; GB/s on the fused pass's algorithmic bytes, 8 S per list (p and the labels
+    read once), for both."""
+    g = torch.Generator(device=dev).manual_seed(7)
+    prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+    y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+    p = torch.softmax(torch.randn(B, S, device=dev, generator=g), 1).contiguous()
+    tab, coef = ops.dcg_table(dev), ops.dcg_coef(S, dev)
+    f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+    k, pk, mg, f1, dcg, bf, bfk, bd, bdk, better = i32(B), torch.zeros(B, device=dev), torch.zeros(B, device=dev), f64(B), f64(B), \
+        f64(B), i32(B), f64(B), i32(B), i32(B)
+    hist, pc, rc, sums = f64(S + 1), f64(S), f64(S), f64(5)
+    wsb = N.query("rlt_cut_report_workspace", B, S)
+    ws = N.workspace(wsb, dev)
+    tau, sharpen = 0.9, 0.9e-3
+
+    def fused():
+        call("rlt_cut_report", ptr(p), N.CUT_ARGMAX, ptr(y), ptr(coef), B, S, N.METRIC_DCG, -1.0, -1.0, tau, sharpen, ptr(tab), 0,
+             ptr(k), ptr(pk), ptr(mg), ptr(f1), ptr(dcg), ptr(bf), ptr(bfk), ptr(bd), ptr(bdk), ptr(better), ptr(hist), ptr(pc), ptr(rc),
+             ptr(sums), ptr(ws), wsb, stream())
+    curves, csums, s2 = f64(3, S + 1), f64(3), f64(2)
+    cwsb = N.query("rlt_truncation_curves_workspace", B, S)
+    cws = N.workspace(cwsb, dev)
+    r = torch.empty(B, S, device=dev)
+
+    def composed():
+        call("rlt_cut_metrics_ex", ptr(p), ptr(y), None, B, S, -1.0, ptr(k), ptr(f1), ptr(dcg), ptr(s2), stream())
+        call("rlt_truncation_curves", ptr(y), B, S, -1.0, ptr(tab), 0, ptr(curves), ptr(bf), ptr(bfk), ptr(bd), ptr(bdk), ptr(csums),
+             ptr(cws), cwsb, stream())
+        call("rlt_reward_matrix_ex", ptr(y), ptr(coef), B, S, N.METRIC_DCG, -1.0, tau, ptr(r), None, stream())
+        rk = r.gather(1, (k.long() - 1).unsqueeze(1))
+        (r > rk).sum(1)
+        torch.softmax(r.double() / tau, 1).sum(0)
+        torch.softmax(p.double() / sharpen, 1).sum(0)
+        torch.bincount(k, minlength=S + 1)
+    times = {"fused": [], "composed": []}
+    for fn in (fused, composed):
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for name, fn in (("fused", fused), ("composed", composed)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    nbytes = 8.0 * B * S
+    mf, mc = (sorted(times[n])[reps // 2] for n in ("fused", "composed"))
+    print(f"cut report fused    B{B} S{S}: {mf * 1e3:9.1f} us  {nbytes / mf / 1e6:8.1f} GB/s algorithmic = {nbytes / mf / 1e6 / 8000:.3f} of 8 TB/s", flush=True)
+    print(f"cut report composed B{B} S{S}: {mc * 1e3:9.1f} us  {nbytes / mc / 1e6:8.1f} GB/s on the same bytes", flush=True)
+    print(f"cut report composed / fused: {mc / mf:.2f}x", flush=True)
+
+
 def probe(B=4096, S=300, E=256):
     """rlt_probe_heads (the probing study's fused probe pass) against the composed path on the same data: one BCE and one
     rerank head on frozen position-major features x (S*B, E) = 1.26 GB.  Fused: x read once, no dx.  Composed: rlt_heads_fwd
