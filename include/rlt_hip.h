@@ -84,8 +84,11 @@ const char* rlt_error_string(int code);
  *   dcg_coef: S floats log2(j+2) (utils/metrics.py:7), required for RLT_METRIC_DCG.
  *   loss_per_list: (B) un-normalised per-list terms; *loss_out = sum(loss_per_list)/B
  *   (KLDivLoss 'batchmean' / the reference's .div(B)).
- *   dp: (B,S) or NULL; receives d(loss_out)/dp (already divided by B).
- *   S <= 1024.
+ *   dp: (B,S) or NULL; receives d(loss_out)/dp (already divided by B).  With dp == NULL the call computes the loss only.
+ *   S <= 1024 (RLT_E_SHAPE beyond).
+ *   Alignment: when S % 4 == 0 every form of the pass reads and writes its rows 16 bytes at a time, so p, labels and each
+ *   (B,S) output that is present - dp here, r_out / q_out of rlt_reward_matrix[_ex] - must be 16-byte aligned: RLT_E_ALIGN
+ *   before any launch otherwise (also for rlt_loss_metrics).  Other S: 4-byte alignment suffices.
  */
 #define RLT_METRIC_F1  0
 #define RLT_METRIC_DCG 1
@@ -111,7 +114,9 @@ int rlt_reward_matrix_ex(const float* labels, const float* dcg_coef, int B, int 
  * the cut metrics of rlt_cut_metrics_ex on the same rows while they are in registers - k_out (B) int32 = argmax_j p + 1 (first
  * maximum), f1_out / dcg_out (B) float64 (DCG with `metric_penalty`, utils/metrics.py:27), sums[0..1] = their batch sums.
  * loss_out = (sum of the per-list terms)/B from a float64 sum.  All outputs required except dp.  Two launches: the pass
- * (two ranked lists per wavefront - one per 32-lane half - when S % 4 == 0 and S <= 384, one per wavefront otherwise; a grid
+ * (when S % 4 == 0, S <= 384 and dp is given: two ranked lists per wavefront - one per 32-lane half - or four - one per
+ * 16-lane row, where rounds of 64 positions waste fewer lanes than rounds of 128: S in 1..64, 129..192 and, for F1, 257..320;
+ * one list per wavefront otherwise; a grid
  * sized to the chip striding over the lists; every wavefront leaves its float64 partial sums in ws) and a one-workgroup
  * fixed-order reduction of those partials (deterministic).  The float64 DCG coefficients 1/log2(j+2) (utils/metrics.py:7) and
  * their prefix sums are read from `dcg_table`, CALLER memory of rlt_dcg_table_bytes() bytes (8-byte aligned) that

@@ -14,6 +14,7 @@
 #include "mt_terms.h"
 #include <cmath>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 
 namespace {
@@ -31,6 +32,8 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 // v_log_f32 / v_rcp_f32 read a denormal input as zero (log -> -inf, rcp -> inf) where the reference's logf / division give
 // finite values (ln 1e-40 = -92.1).  The cut distribution p can underflow into that range (a softmax over 300 logits), so
 // the terms in p scale a denormal argument into the normal range first; an exact 0 still gives -inf / inf as in torch.
+// The reward distribution q = exp(r / tau) / Z reaches that range too once the DCG reward spans more than 87 tau (lists of
+// ~600 positions and more, which only the general pass takes): q ln q of such a q was -inf where the reference's is ~0.
 __device__ __forceinline__ float safe_log(float x) {
     const bool den = x < 1.17549435e-38f;
     return (__builtin_amdgcn_logf(den ? x * 4294967296.f : x) - (den ? 32.f : 0.f)) * 0.6931471805599453f;
@@ -207,13 +210,13 @@ __global__ __launch_bounds__(256) void reward_loss_kernel(RewardArgs a) {
                     term = -(safe_log(p) * q);
                     g = safe_div(-q * a.gscale, p);
                 } else if (a.kind == RLT_LOSS_KL) {          // utils/losses.py:230, kl_div(log p, q)
-                    const float qlq = (q > 0.f) ? q * fast_log(q) : 0.f;
+                    const float qlq = (q > 0.f) ? q * safe_log(q) : 0.f;      // (q underflows into the denormals for S >~ 600)
                     term = qlq - q * safe_log(p);
                     g = safe_div(-q * a.gscale, p);
                 } else {                                     // utils/losses.py:232-233, JS
-                    const float lm = fast_log((p + q) * 0.5f);
+                    const float lm = safe_log((p + q) * 0.5f);
                     const float lp_ = safe_log(p);
-                    const float qlq = (q > 0.f) ? q * fast_log(q) : 0.f;
+                    const float qlq = (q > 0.f) ? q * safe_log(q) : 0.f;
                     const float plp = (p > 0.f) ? p * lp_ : 0.f;
                     term = 0.5f * ((qlq - q * lm) + (plp - p * lm));
                     g = 0.5f * (lp_ - lm) * a.gscale;        // gradient flows through log m AND the target p
@@ -879,12 +882,18 @@ __global__ __launch_bounds__(256) void task_metrics_sum_kernel(const double* __r
 
 extern "C" {
 
-static int reward_args_ok(const float* p, const float* labels, const float* dcg_coef, int B, int S, int metric, int kind) {
+// out0..out2: the (B,S) outputs of the call (dp, r_out, q_out; any may be NULL).  Rows of S % 4 == 0 floats are read AND
+// written 16 bytes at a time by every form of the pass, so each array present has to be 16-byte aligned.
+static int reward_args_ok(const float* p, const float* labels, const float* dcg_coef, int B, int S, int metric, int kind,
+                          const float* out0 = nullptr, const float* out1 = nullptr, const float* out2 = nullptr) {
     RLT_CHECK_ARG(labels && B > 0 && S > 0);
     RLT_CHECK_ARG(metric == RLT_METRIC_F1 || (metric == RLT_METRIC_DCG && dcg_coef));
     RLT_CHECK_ARG(kind >= RLT_LOSS_EXPECT && kind <= RLT_LOSS_JS);
     RLT_CHECK_SHAPE(S <= 1024);
-    if ((S & 3) == 0 && !((!p || rlt_aligned16(p)) && rlt_aligned16(labels))) return RLT_E_ALIGN;
+    if ((S & 3) == 0) {
+        for (const float* a : {p, labels, out0, out1, out2})
+            if (a && !rlt_aligned16(a)) return RLT_E_ALIGN;
+    }
     return 0;
 }
 
@@ -892,7 +901,7 @@ int rlt_reward_loss_ex(const float* p, const float* labels, const float* dcg_coe
                        int metric, float penalty, int kind, float tau,
                        float* loss_per_list, float* loss_out, float* dp, void* stream) {
     RLT_CHECK_ARG(p && loss_per_list);
-    int rc = reward_args_ok(p, labels, dcg_coef, B, S, metric, kind);
+    int rc = reward_args_ok(p, labels, dcg_coef, B, S, metric, kind, dp);
     if (rc) return rc;
     RewardArgs a{p, labels, dcg_coef, loss_per_list, dp, nullptr, nullptr, B, S, metric, kind, tau, 1.0f / (float)B, penalty,
                  nullptr, nullptr, nullptr, -1.0, nullptr, nullptr};
@@ -933,7 +942,7 @@ int rlt_loss_metrics(const float* p, const float* labels, const float* dcg_coef,
                      const void* dcg_table, void* ws, size_t ws_bytes, void* stream) {
     RLT_CHECK_ARG(p && loss_per_list && loss_out && k_out && f1_out && dcg_out && sums && ws && dcg_table);
     if (((uintptr_t)dcg_table & 7u) != 0) return RLT_E_ALIGN;
-    int rc = reward_args_ok(p, labels, dcg_coef, B, S, metric, kind);
+    int rc = reward_args_ok(p, labels, dcg_coef, B, S, metric, kind, dp);
     if (rc) return rc;
     if (ws_bytes < rlt_loss_metrics_workspace(B)) return RLT_E_WORKSPACE;
     RewardArgs a{p, labels, dcg_coef, loss_per_list, dp, nullptr, nullptr, B, S, metric, kind, tau, 1.0f / (float)B, penalty,
@@ -950,7 +959,7 @@ int rlt_loss_metrics(const float* p, const float* labels, const float* dcg_coef,
 int rlt_reward_matrix_ex(const float* labels, const float* dcg_coef, int B, int S, int metric, float penalty, float tau,
                          float* r_out, float* q_out, void* stream) {
     RLT_CHECK_ARG(r_out || q_out);
-    int rc = reward_args_ok(nullptr, labels, dcg_coef, B, S, metric, RLT_LOSS_KL);
+    int rc = reward_args_ok(nullptr, labels, dcg_coef, B, S, metric, RLT_LOSS_KL, r_out, q_out);
     if (rc) return rc;
     RewardArgs a{nullptr, labels, dcg_coef, nullptr, nullptr, r_out, q_out, B, S, metric, RLT_LOSS_KL, tau, 1.0f, penalty,
                  nullptr, nullptr, nullptr, -1.0, nullptr, nullptr};

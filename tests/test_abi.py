@@ -59,6 +59,35 @@ def test_argument_errors_are_reported_not_crashed(native):
     assert lib.rlt_cut_metrics_ex(None, None, None, 1, 1, -1.0, None, None, None, None, None) == -1
 
 
+def test_reward_pass_checks_alignment_and_length_before_any_launch(native):
+    """Rows of S % 4 == 0 floats are read and written 16 bytes at a time by every form of the reward pass: p, labels and each
+    (B,S) output present (dp, r_out, q_out) off 16 bytes is RLT_E_ALIGN, S > 1024 is RLT_E_SHAPE - return codes only, nothing
+    is launched (host buffers, no GPU)."""
+    import ctypes
+    lib = native.load()
+    buf = (ctypes.c_uint8 * (1 << 16))()
+    base = (ctypes.addressof(buf) + 15) // 16 * 16
+    x, off = ctypes.c_void_p(base), ctypes.c_void_p(base + 4)
+    B, S = 2, 8
+    ws = native.query("rlt_loss_metrics_workspace", B)
+    for metric, coef in ((native.METRIC_F1, None), (native.METRIC_DCG, x)):
+        loss = lambda p, y, dp, S=S: lib.rlt_reward_loss_ex(p, y, coef, B, S, metric, -1.0, native.LOSS_JS, 0.85, x, x, dp, None)
+        fused = lambda p, y, dp, S=S: lib.rlt_loss_metrics(p, y, coef, B, S, metric, -1.0, native.LOSS_JS, 0.85, -1.0, x, x, dp,
+                                                           x, x, x, x, x, x, ws, None)
+        matrix = lambda y, r, q, S=S: lib.rlt_reward_matrix_ex(y, coef, B, S, metric, -1.0, 0.85, r, q, None)
+        for fn in (loss, fused):
+            assert fn(off, x, x) == -4 and fn(x, off, x) == -4 and fn(x, x, off) == -4
+            assert fn(off, x, None) == -4 and fn(x, off, None) == -4            # the loss-only form (dp == NULL)
+            assert fn(x, x, x, S=1025) == -2 and fn(x, x, off, S=1025) == -2 and fn(x, x, None, S=1028) == -2
+        assert matrix(off, x, x) == -4 and matrix(x, off, x) == -4 and matrix(x, x, off) == -4
+        assert matrix(x, off, None) == -4 and matrix(x, None, off) == -4
+        assert matrix(x, x, x, S=1025) == -2 and matrix(x, None, None) == -1
+    assert lib.rlt_reward_loss(x, x, None, B, S, native.METRIC_F1, native.LOSS_KL, 1.0, x, x, off, None) == -4
+    assert lib.rlt_reward_matrix(x, None, B, S, native.METRIC_F1, 1.0, off, None, None) == -4
+    assert lib.rlt_task_metrics(x, x, B, 1025, x, x, None, None) == -2
+    assert lib.rlt_heads_fwd(x, x, x, x, 1, 1025, 1, 64, x, None) == -2
+
+
 def test_path_level_entry_points(native):
     """rlt_encoder_layer_fwd/bwd, rlt_bilstm_fwd/bwd, rlt_workspace_bytes: sizes are consistent with the
     documented stash layout and bad arguments are reported (no GPU needed)."""

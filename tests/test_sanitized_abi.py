@@ -59,6 +59,18 @@ lm_b = N.query("rlt_loss_metrics_workspace", B)
 assert lib.rlt_loss_metrics(x, x, None, B, S, 0, -1.0, 3, 0.85, -1.0, x, x, x, x, x, x, x, None, x, lm_b, None) == -1      # no table
 assert lib.rlt_loss_metrics(x, x, None, B, S, 0, -1.0, 3, 0.85, -1.0, x, x, x, x, x, x, x, ctypes.c_void_p(base + 4), x, lm_b, None) == -4
 assert lib.rlt_loss_metrics(x, x, None, B, S, 0, -1.0, 3, 0.85, -1.0, x, x, x, x, x, x, x, x, x, lm_b - 1, None) == -3
+# the reward pass: with S % 4 == 0 every (B,S) array present - p, labels AND the outputs dp / r_out / q_out - off 16 bytes is
+# RLT_E_ALIGN (-4), S = 1025 is RLT_E_SHAPE (-2); both answers come before a launch is formed
+o4 = ctypes.c_void_p(base + 4)
+for S4 in (4, 8, 384, 388, 1024):
+    assert lib.rlt_reward_loss_ex(x, x, None, B, S4, 0, -1.0, 3, 0.85, x, x, o4, None) == -4
+    assert lib.rlt_reward_loss_ex(x, o4, None, B, S4, 0, -1.0, 3, 0.85, x, None, None, None) == -4
+    assert lib.rlt_loss_metrics(x, x, x, B, S4, 1, -0.5, 2, 1.0, -2.0, x, x, o4, x, x, x, x, x, x, lm_b, None) == -4
+    assert lib.rlt_reward_matrix_ex(x, x, B, S4, 1, -1.0, 0.85, o4, None, None) == -4
+    assert lib.rlt_reward_matrix_ex(x, x, B, S4, 1, -1.0, 0.85, x, o4, None) == -4
+assert lib.rlt_reward_loss_ex(x, x, None, B, 1025, 0, -1.0, 3, 0.85, x, x, x, None) == -2
+assert lib.rlt_loss_metrics(x, x, None, B, 1025, 0, -1.0, 3, 0.85, -1.0, x, x, x, x, x, x, x, x, x, lm_b, None) == -2
+assert lib.rlt_reward_matrix_ex(x, None, B, 1025, 0, -1.0, 0.85, x, x, None) == -2
 print("walk ok")
 """
 
