@@ -270,6 +270,28 @@ int rlt_gemm_ex(int ta, int tb, int M, int N, int K,
                 float drop_p, uint32_t seed,
                 void* ws, size_t ws_bytes, int precision, void* stream);
 
+/* What the last rlt_gemm / rlt_gemm_ex / rlt_gemm_bits call of the CALLING THREAD decided (tests: tests/test_gemm_dispatch_gpu.py
+ * asserts that a case reaches the kernel its id names).  Written on the host in the branch that launches; no device work, no
+ * influence on the choice.  family RLT_GEMM_NONE: no product has been launched by this thread yet, or the last call returned
+ * before its launch (argument / workspace error).
+ *   fast       the branch-free loaders (gemm_kernel, gemm3_kernel; 1 for the families that have no other loader)
+ *   persistent the workgroups walk the output tiles (gemm3b / gemm6c / gemm6e)
+ *   ns, kchunk, slab_xcd   the final split-K plan: slabs, K per slab, slabs pinned to XCDs (1-D grid)
+ *   epilogue, narrow       gemm6s only: its epilogue code (0 plain, 1 ReLU, 2 ReLU + bits out, 3 bits in), 128-column panels */
+#define RLT_GEMM_NONE   0
+#define RLT_GEMM_F32    1   /* gemm_kernel: exact fp32, 128 x 128 */
+#define RLT_GEMM_3      2   /* gemm3_kernel: bf16x3, 128 x 128 */
+#define RLT_GEMM_3B     3   /* gemm3b_kernel: bf16x3, 256 x 256 */
+#define RLT_GEMM_6      4   /* gemm6_kernel: bf16x6, 256 x 128 */
+#define RLT_GEMM_6B     5   /* gemm6b_kernel: bf16x6, 256 x 256, one K tile per slab */
+#define RLT_GEMM_6C     6   /* gemm6c_kernel: bf16x6, 256 x 256, two wavefronts per SIMD */
+#define RLT_GEMM_6E     7   /* gemm6e_kernel: bf16x6, 256 x 256, one wavefront per SIMD */
+#define RLT_GEMM_6S     8   /* gemm6s_kernel: bf16x6, weights-stationary K = 256 / 128 */
+typedef struct rlt_gemm_dispatch {
+    int family, ta, tb, fast, persistent, ns, kchunk, slab_xcd, epilogue, narrow;
+} rlt_gemm_dispatch;
+int rlt_gemm_last_dispatch(rlt_gemm_dispatch* out);
+
 /* The FFN pair of rlt_gemm_ex epilogues with a 1-bit-per-element mask instead of the fp32 activation
  * (nn.TransformerEncoderLayer's linear1 -> ReLU -> dropout forward and the dH = (dY W2) * mask backward):
  *   relu_bits_out != NULL (flags must hold RLT_GEMM_RELU): C = dropout(relu(op(A) op(B) + bias)) with the keep mask of

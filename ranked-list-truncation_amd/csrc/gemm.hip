@@ -44,6 +44,12 @@ struct GemmArgs {
     int ldbits;
 };
 
+// rlt_gemm_last_dispatch: called by every launcher right before its launch, with the kernel it is about to start
+inline void note_dispatch(int family, bool ta, bool tb, bool fast, bool persistent, const GemmArgs& g, int ns) {
+    rlt_gemm_dispatch_rec = rlt_gemm_dispatch{family, ta ? 1 : 0, tb ? 1 : 0, fast ? 1 : 0, persistent ? 1 : 0,
+                                              ns, g.kchunk, g.slab_xcd, 0, 0};
+}
+
 // (tile, K slab) of this workgroup.
 //  * no split-K, or a split count that is not a multiple of 8: XCD-aware bijective remap of the flat tile id (the
 //    tiles an XCD runs are contiguous and share operand panels in that XCD's L2); slab = blockIdx.z.
@@ -956,6 +962,7 @@ int launch_gemm3b(GemmArgs g, int ns, hipStream_t st) {
         if (want && persist_wgs > 0 && ns == 1 && g.K / BK3 >= 2 && tiles > persist_wgs && persist_wgs % 8 == 0) {
             int rc = rlt_allow_lds(gemm3b_kernel<TA, TB, true>, shm);
             if (rc) return rc;
+            note_dispatch(RLT_GEMM_3B, TA, TB, true, true, g, ns);
             hipLaunchKernelGGL((gemm3b_kernel<TA, TB, true>), dim3(persist_wgs), dim3(512), shm, st, g);
             return RLT_LAUNCH_RESULT();
         }
@@ -963,6 +970,7 @@ int launch_gemm3b(GemmArgs g, int ns, hipStream_t st) {
     int rc = rlt_allow_lds(gemm3b_kernel<TA, TB>, shm);
     if (rc) return rc;
     dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
+    note_dispatch(RLT_GEMM_3B, TA, TB, true, false, g, ns);
     hipLaunchKernelGGL((gemm3b_kernel<TA, TB>), grid, dim3(512), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
@@ -1302,6 +1310,7 @@ int launch_gemm6b(GemmArgs g, int ns, hipStream_t st) {
     int rc = rlt_allow_lds(gemm6b_kernel<TA, TB>, shm);
     if (rc) return rc;
     dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
+    note_dispatch(RLT_GEMM_6B, TA, TB, true, false, g, ns);
     hipLaunchKernelGGL((gemm6b_kernel<TA, TB>), grid, dim3(512), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
@@ -1568,6 +1577,7 @@ int launch_gemm6c(GemmArgs g, int ns, hipStream_t st) {
         if (persist_wgs > 0 && ns == 1 && tiles > persist_wgs && persist_wgs % 8 == 0) {
             int rc = rlt_allow_lds(gemm6c_kernel<TA, TB, true>, shm);
             if (rc) return rc;
+            note_dispatch(RLT_GEMM_6C, TA, TB, true, true, g, ns);
             hipLaunchKernelGGL((gemm6c_kernel<TA, TB, true>), dim3(persist_wgs), dim3(512), shm, st, g);
             return RLT_LAUNCH_RESULT();
         }
@@ -1575,6 +1585,7 @@ int launch_gemm6c(GemmArgs g, int ns, hipStream_t st) {
     int rc = rlt_allow_lds(gemm6c_kernel<TA, TB, false>, shm);
     if (rc) return rc;
     dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
+    note_dispatch(RLT_GEMM_6C, TA, TB, true, false, g, ns);
     hipLaunchKernelGGL((gemm6c_kernel<TA, TB, false>), grid, dim3(512), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
@@ -1845,6 +1856,7 @@ int launch_gemm6e(GemmArgs g, int ns, hipStream_t st) {
         if (persist_wgs > 0 && ns == 1 && tiles > persist_wgs && persist_wgs % 8 == 0) {
             int rc = rlt_allow_lds(gemm6e_kernel<TA, TB, true>, shm);
             if (rc) return rc;
+            note_dispatch(RLT_GEMM_6E, TA, TB, true, true, g, ns);
             hipLaunchKernelGGL((gemm6e_kernel<TA, TB, true>), dim3(persist_wgs), dim3(256), shm, st, g);
             return RLT_LAUNCH_RESULT();
         }
@@ -1852,6 +1864,7 @@ int launch_gemm6e(GemmArgs g, int ns, hipStream_t st) {
     int rc = rlt_allow_lds(gemm6e_kernel<TA, TB, false>, shm);
     if (rc) return rc;
     dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
+    note_dispatch(RLT_GEMM_6E, TA, TB, true, false, g, ns);
     hipLaunchKernelGGL((gemm6e_kernel<TA, TB, false>), grid, dim3(256), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
@@ -1869,23 +1882,25 @@ int launch_gemm6(GemmArgs g, int ns, hipStream_t st) {
     int rc = rlt_allow_lds(gemm6_kernel<TA, TB>, shm);
     if (rc) return rc;
     dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
+    note_dispatch(RLT_GEMM_6, TA, TB, true, false, g, ns);
     hipLaunchKernelGGL((gemm6_kernel<TA, TB>), grid, dim3(512), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
 
 template <bool TA, bool TB, bool FAST>
-int launch_gemm3_v(const GemmArgs& g, dim3 grid, hipStream_t st) {
+int launch_gemm3_v(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
     const size_t shm = (size_t)2 * 4 * TILE3 * sizeof(uint16_t);
     int rc = rlt_allow_lds(gemm3_kernel<TA, TB, FAST>, shm);
     if (rc) return rc;
+    note_dispatch(RLT_GEMM_3, TA, TB, FAST, false, g, ns);
     hipLaunchKernelGGL((gemm3_kernel<TA, TB, FAST>), grid, dim3(256), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
 bool gemm_fast_ok(const GemmArgs& g, bool ta, bool tb);
 template <bool TA, bool TB>
-int launch_gemm3(const GemmArgs& g, dim3 grid, hipStream_t st) {
-    if (gemm_fast_ok(g, TA, TB)) return launch_gemm3_v<TA, TB, true>(g, grid, st);
-    return launch_gemm3_v<TA, TB, false>(g, grid, st);
+int launch_gemm3(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
+    if (gemm_fast_ok(g, TA, TB)) return launch_gemm3_v<TA, TB, true>(g, grid, ns, st);
+    return launch_gemm3_v<TA, TB, false>(g, grid, ns, st);
 }
 
 // C = sum_z slab[z] (+bias, relu, accumulate); fixed order => deterministic.  Four independent partial sums per
@@ -1948,10 +1963,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g, int nspl
 }
 
 template <bool TA, bool TB, int BK, int OCC, bool FAST>
-int launch_gemm_v(const GemmArgs& g, dim3 grid, hipStream_t st) {
+int launch_gemm_v(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
     const size_t shm = (size_t)4 * BK * LDT * sizeof(float);
     int rc = rlt_allow_lds(gemm_kernel<TA, TB, BK, OCC, FAST>, shm);
     if (rc) return rc;
+    note_dispatch(RLT_GEMM_F32, TA, TB, FAST, false, g, ns);
     hipLaunchKernelGGL((gemm_kernel<TA, TB, BK, OCC, FAST>), grid, dim3(256), shm, st, g);
     return RLT_LAUNCH_RESULT();
 }
@@ -1965,9 +1981,9 @@ bool gemm_fast_ok(const GemmArgs& g, bool ta, bool tb) {
     return true;
 }
 template <bool TA, bool TB, int BK>
-int launch_gemm(const GemmArgs& g, dim3 grid, hipStream_t st) {
-    if (gemm_fast_ok(g, TA, TB)) return launch_gemm_v<TA, TB, BK, 4, true>(g, grid, st);
-    return launch_gemm_v<TA, TB, BK, 4, false>(g, grid, st);
+int launch_gemm(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
+    if (gemm_fast_ok(g, TA, TB)) return launch_gemm_v<TA, TB, BK, 4, true>(g, grid, ns, st);
+    return launch_gemm_v<TA, TB, BK, 4, false>(g, grid, ns, st);
 }
 
 // 0 = exact fp32 MFMA (parity mode), 1 = split-bf16 (bf16x3), 2 = fp32-faithful six-product split (bf16x6);
@@ -2096,7 +2112,15 @@ int ew_grid(size_t n) { size_t g = (n + 1023) / 1024; return (int)(g < 1 ? 1 : (
 
 }  // namespace
 
+thread_local rlt_gemm_dispatch rlt_gemm_dispatch_rec = {};
+
 extern "C" {
+
+int rlt_gemm_last_dispatch(rlt_gemm_dispatch* out) {
+    RLT_CHECK_ARG(out);
+    *out = rlt_gemm_dispatch_rec;
+    return 0;
+}
 
 size_t rlt_gemm_workspace(int ta, int tb, int M, int N, int K) {
     (void)ta; (void)tb;
@@ -2120,6 +2144,7 @@ static int gemm_run(int ta, int tb, int M, int N, int K,
                     const float* relu_mask, int ldmask, float mask_scale, float* colsum_a,
                     float drop_p, uint32_t seed, uint32_t* bits_out, const uint32_t* bits_in,
                     void* ws, size_t ws_bytes, void* stream) {
+    rlt_gemm_dispatch_rec = rlt_gemm_dispatch{};          // RLT_GEMM_NONE until a branch below launches
     RLT_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0);
     RLT_CHECK_ARG(lda >= (ta ? M : K) && ldb >= (tb ? K : N) && ldc >= N);
     RLT_CHECK_ARG(!relu_mask || ldmask >= N);
@@ -2195,15 +2220,15 @@ static int gemm_run(int ta, int tb, int M, int N, int K,
         else if (ta && !tb) rc = launch_gemm3b<true, false>(g, ns, st);
         else rc = launch_gemm3b<true, true>(g, ns, st);
     } else if (gemm_mode() == 1) {
-        if (!ta && tb) rc = launch_gemm3<false, true>(g, grid, st);
-        else if (!ta && !tb) rc = launch_gemm3<false, false>(g, grid, st);
-        else if (ta && !tb) rc = launch_gemm3<true, false>(g, grid, st);
-        else rc = launch_gemm3<true, true>(g, grid, st);
+        if (!ta && tb) rc = launch_gemm3<false, true>(g, grid, ns, st);
+        else if (!ta && !tb) rc = launch_gemm3<false, false>(g, grid, ns, st);
+        else if (ta && !tb) rc = launch_gemm3<true, false>(g, grid, ns, st);
+        else rc = launch_gemm3<true, true>(g, grid, ns, st);
     } else {
-        if (!ta && tb) rc = launch_gemm<false, true, 16>(g, grid, st);
-        else if (!ta && !tb) rc = launch_gemm<false, false, 16>(g, grid, st);
-        else if (ta && !tb) rc = launch_gemm<true, false, 16>(g, grid, st);
-        else rc = launch_gemm<true, true, 16>(g, grid, st);
+        if (!ta && tb) rc = launch_gemm<false, true, 16>(g, grid, ns, st);
+        else if (!ta && !tb) rc = launch_gemm<false, false, 16>(g, grid, ns, st);
+        else if (ta && !tb) rc = launch_gemm<true, false, 16>(g, grid, ns, st);
+        else rc = launch_gemm<true, true, 16>(g, grid, ns, st);
     }
     if (rc) return rc;
     if (ns > 1)

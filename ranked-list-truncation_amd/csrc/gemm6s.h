@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/rlt_hip.h"
 
 struct Gemm6sArgs {
     const float* A; const float* B; float* C;      // C[M x N] = A[M x 256] op(B) (+ bias + bias2)
@@ -17,3 +18,5 @@ struct Gemm6sArgs {
 // mask word - no consumer reads them (rlt_gemm_bits indexes rows < M), but the word differs from the tiled kernels' (which write 0 there).
 bool rlt_gemm6s_ok(const Gemm6sArgs& g);
 int rlt_gemm6s_launch(const Gemm6sArgs& g, bool tb, bool relu, void* stream);      // 0 or a hip error code (bits_out needs relu; not both bit pointers)
+// the record rlt_gemm_last_dispatch returns: written by the branch that launches (gemm_run, rlt_gemm6s_launch), host only
+extern thread_local rlt_gemm_dispatch rlt_gemm_dispatch_rec;

@@ -303,14 +303,15 @@ int rlt_gemm6s_launch(const Gemm6sArgs& g, bool tb, bool relu, void* stream) {
     if (nstream < 1) nstream = 1;
     if (nstream > nblk) nstream = nblk;
     const size_t lds = g.K == 256 ? gs_lds<8>() : gs_lds<4>();
+    const int epi = g.bits_in ? 3 : g.bits_out ? 2 : relu ? 1 : 0;
     auto go = [&](auto kern) {
         const int rc = rlt_allow_lds(kern, lds);
         if (rc) return rc;
+        rlt_gemm_dispatch_rec = rlt_gemm_dispatch{RLT_GEMM_6S, 0, tb ? 1 : 0, 1, 0, 1, g.K, 0, epi, narrow ? 1 : 0};
         hipLaunchKernelGGL(kern, dim3(npanel * nstream), dim3(256), lds, rlt_stream(stream), g);
         return 0;
     };
     if (g.bits_out && !relu) return -1;
-    const int epi = g.bits_in ? 3 : g.bits_out ? 2 : relu ? 1 : 0;
     if (narrow) {
         if (g.K != 128 || epi >= 2) return -1;
         return tb ? (epi ? go(gemm6s_kernel<4, 2, true, 1>) : go(gemm6s_kernel<4, 2, true, 0>))

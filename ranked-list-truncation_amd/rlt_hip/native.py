@@ -65,6 +65,7 @@ _SIGNATURES = {
     "rlt_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, P, c_size_t, c_int, P]),
     "rlt_gemm_ex": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, P, c_int, c_float,
                             P, c_float, c_uint32, P, c_size_t, c_int, P]),
+    "rlt_gemm_last_dispatch": (c_int, [P]),
     "rlt_dropout_mask": (c_int, [c_uint32, c_size_t, c_int, c_float, P, P]),
     "rlt_attention_dropout_mask": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
     "rlt_attention_dropout_mask_range": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
@@ -142,6 +143,24 @@ SPARSE_INTS = ("Dn", "n_docs", "V", "n_chunks", "n_multi")
 class SparseBatchPtrs(ctypes.Structure):
     """rlt_sparse_batch: 12 device pointers in SPARSE_POINTERS order, then the five ints of SPARSE_INTS."""
     _fields_ = [(f, c_void_p) for f in SPARSE_POINTERS] + [(f, c_int) for f in SPARSE_INTS]
+
+
+GEMM_FAMILIES = ("none", "gemm", "gemm3", "gemm3b", "gemm6", "gemm6b", "gemm6c", "gemm6e", "gemm6s")      # RLT_GEMM_NONE .. RLT_GEMM_6S
+GEMM_DISPATCH_FIELDS = ("family", "ta", "tb", "fast", "persistent", "ns", "kchunk", "slab_xcd", "epilogue", "narrow")
+
+
+class GemmDispatch(ctypes.Structure):
+    """rlt_gemm_dispatch: what the calling thread's last rlt_gemm / rlt_gemm_ex / rlt_gemm_bits call launched."""
+    _fields_ = [(f, c_int) for f in GEMM_DISPATCH_FIELDS]
+
+
+def gemm_last_dispatch():
+    """-> dict of GEMM_DISPATCH_FIELDS, `family` as its name in GEMM_FAMILIES."""
+    d = GemmDispatch()
+    check(load().rlt_gemm_last_dispatch(ctypes.byref(d)), "rlt_gemm_last_dispatch")
+    out = {f: int(getattr(d, f)) for f in GEMM_DISPATCH_FIELDS}
+    out["family"] = GEMM_FAMILIES[out["family"]]
+    return out
 
 
 def encoder_ptrs(tensors):

@@ -5,6 +5,8 @@ The checks live in tools/gpu_probe.py (one section per kernel family, every case
 |error| vs tolerance); each test runs a section and requires every case to be within tolerance:
 
     gemm        rlt_gemm all transpose modes, ragged sizes, K=3, split-K, bias/ReLU/accumulate; rlt_colsum
+                (per-branch coverage - every kernel family, layout and epilogue with exact operands, the dispatch asserted:
+                tests/test_gemm_dispatch_gpu.py)
     losses      every criterion x metric against the reference's golden losses and dL/dp (edge rows:
                 no relevant doc, all relevant, single positive first/last), ragged S, MtCutLoss
     metrics     Metric.f1 / Metric.dcg known answers of the reference, argmax cut positions
