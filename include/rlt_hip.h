@@ -397,6 +397,59 @@ int rlt_list_attention_bwd_dkv(const float* qkv, const float* dout, const float*
                                int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, int precision, void* stream);
 int rlt_list_attention_bwd_dq(const float* qkv, const float* dout, const float* lse, const void* images, void* ws, size_t ws_bytes,
                               int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, int precision, void* stream);
+/* What the entry points above decide for one call (csrc/attention_plan.h: the decision is taken once per call, there; tests:
+ * tests/test_attention_plan.py, tests/test_attention_dispatch_gpu.py).  Host only: no device work, no influence on the choice.
+ * have_images: the call is given a usable `images` buffer (non-NULL; for the pipelined forwards also 16-byte aligned and
+ * images_bytes long).  Errors: RLT_E_ARG (out NULL, non-positive S / B / H, drop_p outside [0, 1), precision), RLT_E_SHAPE (HD).
+ *   fwd, dkv, dq     the kernel of rlt_list_attention_fwd / _bwd_dkv / _bwd_dq, an RLT_ATTN_* code
+ *   fwd_fixup        the kernel of the forward's second launch over the workgroups the pipelined forward flagged, or RLT_ATTN_NONE
+ *   *_prepare        what the entry point writes before its kernel, a mask of RLT_ATTN_PREP_*: the forward into `images` (the
+ *                    blocks in the order of the set bits: Q | K | V, or K | V), _bwd_prepare / _bwd_dkv / _bwd_dq into ws
+ *   images_kind, images_bytes, images_retained   the forward's `images` (= rlt_list_attention_fwd_workspace and
+ *                    _images_retained); flags_offset / flags_bytes: the flag words of the fix-up launch at its end
+ *   ws_kind, delta_bytes, ws_extra_bytes, ws_bytes   the backward workspace: delta, then ws_extra_bytes of ws_kind
+ *                    (ws_bytes = the sum = rlt_list_attention_bwd_workspace)
+ *   ws_prepare_bytes, ws_part_bytes   what _bwd_prepare and _bwd_dkv / _bwd_dq require of ws_bytes in THIS call (with
+ *                    have_images = 0 they do not use - and _bwd_prepare does not ask for - tile records behind delta) */
+#define RLT_ATTN_NONE           0
+#define RLT_ATTN_F32            1   /* attn_*_kernel: exact fp32, 32x32x2 MFMA (dK+dV: two workgroups per CU) */
+#define RLT_ATTN_F32_SB         2   /* ... forward / dQ at head dim 64: single-buffered, three workgroups per CU */
+#define RLT_ATTN_F32_OCC1       3   /* ... dK+dV in the 512-register form (head dim 128; RLT_DKV_OCC=1) */
+#define RLT_ATTN_F32_HD16       4   /* attn16_*_kernel: exact fp32 at head dim 16, 16x16x4 MFMA */
+#define RLT_ATTN_X3             5   /* attn3_*_kernel: bf16x3 from tile records */
+#define RLT_ATTN_X6             6   /* attn6_{fwd,bwd_dkv,bwd_dq}_kernel: bf16x6, two wavefronts per SIMD */
+#define RLT_ATTN_X6_IMG         7   /* ... staging pre-split tile images (RLT_ATTN6_IMG=1) */
+#define RLT_ATTN_X6_PP          8   /* attn6_fwd_pp_kernel: head dim 64 ping-pong forward */
+#define RLT_ATTN_X6_PP_IMG      9   /* ... staging pre-split tile images */
+#define RLT_ATTN_X6_DKV1        10  /* attn6_bwd_dkv1_kernel: head dim 64 dK+dV, one wavefront per SIMD */
+#define RLT_ATTN_X6_DQ1         11  /* attn6_bwd_dq1_kernel: head dim 64 dQ, one wavefront per SIMD */
+#define RLT_ATTN_X6N_2W         12  /* attn6n_*_kernel<.., false>: head dim 16, two wavefronts per SIMD, fewer than 512 lists */
+#define RLT_ATTN_X6N_2W_SEEDED  13  /* attn6n_*_kernel<.., true>: ... 512 lists and more (score accumulators seeded with -lse, -delta) */
+#define RLT_ATTN_X6N_PIPE       14  /* attn6n_fwd1_kernel / attn6n_bwd1_kernel: head dim 16 pipelined, from tile images */
+#define RLT_ATTN_X6H_PIPE       15  /* attn6h_fwd1_kernel: head dim 64 pipelined forward, from tile images */
+#define RLT_ATTN_PREP_Q      1
+#define RLT_ATTN_PREP_K      2
+#define RLT_ATTN_PREP_V      4
+#define RLT_ATTN_PREP_DO     8
+#define RLT_ATTN_PREP_SEEDS  16     /* the rows' -lse, -delta (head dim 16 pipelined backward) */
+#define RLT_ATTN_PREP_DELTA  32     /* delta = rowsum(dout * out) */
+#define RLT_ATTN_IMAGES_NONE    0
+#define RLT_ATTN_IMAGES_X3_QKV  1   /* bf16x3 tile records of Q, K, V (retained) */
+#define RLT_ATTN_IMAGES_X6_QKV  2   /* bf16x6 tile images of Q, K, V (RLT_ATTN6_IMG=1, retained) */
+#define RLT_ATTN_IMAGES_X6N_KV  3   /* head dim 16 pipelined forward: K images | V images | flag words (scratch) */
+#define RLT_ATTN_IMAGES_X6H_KV  4   /* head dim 64 pipelined forward: the same */
+#define RLT_ATTN_WS_DELTA       0   /* nothing behind delta */
+#define RLT_ATTN_WS_X3_DO       1   /* bf16x3 dO tile records */
+#define RLT_ATTN_WS_X6_DO       2   /* bf16x6 dO tile images (RLT_ATTN6_IMG=1) */
+#define RLT_ATTN_WS_X6N_BLOCKS  3   /* head dim 16 pipelined backward: image blocks Q | K | V | dO, then the seeds */
+typedef struct rlt_attention_plan {
+    int fwd, fwd_fixup, dkv, dq;
+    int fwd_prepare, bwd_prepare, dkv_prepare, dq_prepare;
+    int images_kind, images_retained, ws_kind;
+    size_t images_bytes, flags_offset, flags_bytes;
+    size_t delta_bytes, ws_extra_bytes, ws_bytes, ws_prepare_bytes, ws_part_bytes;
+} rlt_attention_plan;
+int rlt_list_attention_plan(int S, int B, int H, int HD, float drop_p, int have_images, int precision, rlt_attention_plan* out);
 /* keep-mask of the attention-probability dropout as data (tests, small B): out (S,H,B,B) =
  * keep ? 1/(1-p) : 0 for (position, head, query, key) */
 int rlt_attention_dropout_mask(uint32_t seed, int S, int B, int H, float p, float* out, void* stream);

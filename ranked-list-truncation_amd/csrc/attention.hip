@@ -490,17 +490,13 @@ __global__ __launch_bounds__(256, SB ? 3 : (HD <= 64 ? 2 : 1)) void attn_bwd_dq_
 }
 
 template <int HD> size_t fwd_smem(bool sb = false) { return (size_t)(sb ? 2 : 4) * KT * (HD + 4) * sizeof(float); }
-// head dim 64 forward / dQ: the single-buffer, three-workgroups-per-CU form (RLT_ATTN_SB=0: the double-buffered one)
-static bool attn_sb() {
-    static const bool v = [] { const char* e = getenv("RLT_ATTN_SB"); return !e || atoi(e) != 0; }();
-    return v;
-}
 template <int HD> size_t dkv_smem() { return (size_t)(4 * KT * (HD + 4) + 4 * KT) * sizeof(float); }
 
+// SB (RLT_ATTN_F32_SB): the single-buffer, three-workgroups-per-CU form of the forward / dQ kernel; head dim 64 only
 template <int HD, bool DROP>
-int launch_fwd_t(const AttnArgs& a, hipStream_t st) {
+int launch_fwd_t(bool sb, const AttnArgs& a, hipStream_t st) {
     const int grid = a.S * a.H * rlt_cdiv(a.B, QT);
-    if (HD == 64 && attn_sb()) {
+    if (HD == 64 && sb) {
         int rc = rlt_allow_lds(attn_fwd_kernel<HD, DROP, true>, fwd_smem<HD>(true));
         if (rc) return rc;
         hipLaunchKernelGGL((attn_fwd_kernel<HD, DROP, true>), dim3(grid), dim3(256), fwd_smem<HD>(true), st, a);
@@ -511,11 +507,11 @@ int launch_fwd_t(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((attn_fwd_kernel<HD, DROP, false>), dim3(grid), dim3(256), fwd_smem<HD>(), st, a);
     return RLT_LAUNCH_RESULT();
 }
+// occ1 (RLT_ATTN_F32_OCC1): the 512-register form (all there is at head dim 128)
 template <int HD, bool DROP>
-int launch_dkv_t(const AttnArgs& a, hipStream_t st) {
+int launch_dkv_t(bool occ1, const AttnArgs& a, hipStream_t st) {
     const int grid = a.S * a.H * rlt_cdiv(a.B, QT);
-    static const int occ = [] { const char* e = getenv("RLT_DKV_OCC"); return (e && atoi(e) == 1) ? 1 : 2; }();
-    if (occ == 2 && HD <= 64) {          // head dim 128 needs the 512-register form
+    if (!occ1 && HD <= 64) {
         int rc = rlt_allow_lds(attn_bwd_dkv_kernel<HD, 2, DROP>, dkv_smem<HD>());
         if (rc) return rc;
         hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, 2, DROP>), dim3(grid), dim3(256), dkv_smem<HD>(), st, a);
@@ -527,9 +523,9 @@ int launch_dkv_t(const AttnArgs& a, hipStream_t st) {
     return RLT_LAUNCH_RESULT();
 }
 template <int HD, bool DROP>
-int launch_dq_t(const AttnArgs& a, hipStream_t st) {
+int launch_dq_t(bool sb, const AttnArgs& a, hipStream_t st) {
     const int grid = a.S * a.H * rlt_cdiv(a.B, QT);
-    if (HD == 64 && attn_sb() && getenv("RLT_ATTN_SB_DQ")) {       // (at the 168-register cap the dQ kernel spills 80 registers: off)
+    if (HD == 64 && sb) {       // (at the 168-register cap the dQ kernel spills 80 registers: off unless RLT_ATTN_SB_DQ is set)
         int rc = rlt_allow_lds(attn_bwd_dq_kernel<HD, DROP, true>, fwd_smem<HD>(true));
         if (rc) return rc;
         hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, DROP, true>), dim3(grid), dim3(256), fwd_smem<HD>(true), st, a);
@@ -541,24 +537,11 @@ int launch_dq_t(const AttnArgs& a, hipStream_t st) {
     return RLT_LAUNCH_RESULT();
 }
 // dropout is a template parameter: hipcc if-converts a run-time `drop_p > 0` test and executes the hash regardless
-template <int HD> int launch_fwd(const AttnArgs& a, hipStream_t st) {
-    return a.drop_p > 0.f ? launch_fwd_t<HD, true>(a, st) : launch_fwd_t<HD, false>(a, st);
-}
-template <int HD> int launch_dkv(const AttnArgs& a, hipStream_t st) {
-    return a.drop_p > 0.f ? launch_dkv_t<HD, true>(a, st) : launch_dkv_t<HD, false>(a, st);
-}
-template <int HD> int launch_dq(const AttnArgs& a, hipStream_t st) {
-    return a.drop_p > 0.f ? launch_dq_t<HD, true>(a, st) : launch_dq_t<HD, false>(a, st);
-}
-
-AttnArgs bwd_args(const float* qkv, const float* dout, const float* lse, const float* delta,
-                  int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv) {
-    AttnArgs a{};
-    a.qkv = qkv; a.dout = dout; a.lse = lse; a.delta = delta; a.dqkv = dqkv;
-    a.S = S; a.B = B; a.H = H;
-    a.scale = 1.0f / sqrtf((float)HD);
-    a.drop_p = drop_p; a.drop_thr = rlt_drop_threshold(drop_p); a.seed = seed;
-    return a;
+template <int HD> int launch_f32(int kernel, int which, const AttnArgs& a, hipStream_t st) {
+    const bool alt = kernel != RLT_ATTN_F32;      // the part's other form: _F32_SB (forward, dQ) or _F32_OCC1 (dK+dV)
+    if (which == 0) return a.drop_p > 0.f ? launch_fwd_t<HD, true>(alt, a, st) : launch_fwd_t<HD, false>(alt, a, st);
+    if (which == 1) return a.drop_p > 0.f ? launch_dkv_t<HD, true>(alt, a, st) : launch_dkv_t<HD, false>(alt, a, st);
+    return a.drop_p > 0.f ? launch_dq_t<HD, true>(alt, a, st) : launch_dq_t<HD, false>(alt, a, st);
 }
 
 __global__ __launch_bounds__(256) void dropout_mask_kernel(uint32_t seed, size_t rows, int cols, float p, float* out) {
@@ -579,47 +562,24 @@ __global__ __launch_bounds__(256) void attn_dropout_mask_kernel(uint32_t seed, i
 
 }  // namespace
 
-// RLT_ATTN_MODE=fp32|bf16x3 forces the attention family into one mode whatever the call's precision (A/B runs): -1 = not set
-static int attn_forced() {
-    static const int forced = [] {
-        const char* e = getenv("RLT_ATTN_MODE");
-        if (!e) return -1;
-        return (!strcmp(e, "bf16x3") || !strcmp(e, "1")) ? 1 : 0;
-    }();
-    return forced;
-}
-// 0 = exact fp32 MFMA kernels (parity mode) or, in bf16x6 mode, the six-product kernels (attn6_use), 1 = split-bf16 kernels of
-// attention3.hip
-static int attn_mode_any() {
-    const int forced = attn_forced();
-    return forced >= 0 ? forced : (rlt_precision() == RLT_PRECISION_BF16X3 ? 1 : 0);
-}
-// head dims 16 / 32 / 64 have split-bf16 kernels; 128 (PLECut: d_model 256, 2 heads, models/PLECut.py:56) runs on the
-// exact-fp32 kernels in either mode (a correct, unhurried instantiation: it is not on a benchmarked configuration)
-static int attn_mode(int HD) { return HD <= 64 ? attn_mode_any() : 0; }
-static bool hd_ok(int HD) { return HD == 16 || HD == 32 || HD == 64 || HD == 128; }
-// bf16x6 mode: the six-product kernels of attention6.hip where they exist (head dims 16 / 32 / 64); RLT_ATTN6=0 - or a forced
-// RLT_ATTN_MODE - keeps them out (A/B runs)
-static bool attn6_use(int HD, float drop_p) {
-    static const bool on = [] { const char* e = getenv("RLT_ATTN6"); return !e || atoi(e) != 0; }();
-    (void)drop_p;
-    return on && attn_forced() < 0 && rlt_precision() == RLT_PRECISION_BF16X6 && HD <= 64;
-}
-// RLT_ATTN6_IMG=1: ... staged from pre-split tile images (a prepare pass per call, LDS-DMA in the kernels) instead of every
-// workgroup splitting its tiles itself.  Off by default: measured at 4096 x 60 positions it takes the 176-352 split instructions per
-// tile out of the kernels (dQ 7.16 -> 6.82 ms, dK+dV 10.63 -> 10.50, ping-pong forward 9,900 -> 9,140 cycles per tile) and gives the
-// same time back in the two prepare passes (0.45 + 0.22 ms) - the kernels wait at their two barriers per tile for the staging
-// LATENCY, not for its instructions (profiles/r03_notes.md).  It is the staging a double-buffered form of dQ / dK+dV needs.
-static bool attn6_img(int HD) {
-    static const bool on = [] { const char* e = getenv("RLT_ATTN6_IMG"); return e && atoi(e) != 0; }();
-    return on && attn6_use(HD, 0.f);
+// kernel: RLT_ATTN_F32, or the part's other form - _F32_SB for the forward and dQ at head dim 64, _F32_OCC1 for dK+dV (the only
+// dK+dV form at head dim 128)
+int rlt_attn_f32_run(int kernel, int which, const AttnArgs& a, int HD, hipStream_t st) {
+    RLT_CHECK_ARG(which >= 0 && which <= 2);
+    if (which == 1) RLT_CHECK_ARG(kernel == RLT_ATTN_F32_OCC1 || (kernel == RLT_ATTN_F32 && HD <= 64));
+    else RLT_CHECK_ARG(kernel == RLT_ATTN_F32 || (kernel == RLT_ATTN_F32_SB && HD == 64));
+    if (HD == 128) return launch_f32<128>(kernel, which, a, st);
+    if (HD == 64) return launch_f32<64>(kernel, which, a, st);
+    if (HD == 32) return launch_f32<32>(kernel, which, a, st);
+    if (HD == 16) return launch_f32<16>(kernel, which, a, st);
+    return RLT_E_ARG;
 }
 
-// head dim 16 in the exact-fp32 mode: the 16x16x4-MFMA kernels of attention16.hip (RLT_ATTN16=0: the 32x32x2 kernels of this
-// file, whose d-indexed products are half padding at 16)
-static bool attn16_use() {
-    static const bool on = [] { const char* e = getenv("RLT_ATTN16"); return !e || atoi(e) != 0; }();
-    return on;
+int rlt_attn_delta_run(const float* out, const float* dout, int S, int B, int H, int HD, float* delta, hipStream_t st) {
+    const size_t T = (size_t)S * B;
+    const int dgrid = (int)((T + 3) / 4 > 4096 ? 4096 : (T + 3) / 4);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, st, out, dout, S, B, H, HD, delta);
+    return RLT_LAUNCH_RESULT();
 }
 
 extern "C" {
@@ -640,232 +600,6 @@ int rlt_attention_dropout_mask_range(uint32_t seed, int pair0, int npair, int B,
     RLT_CHECK_ARG(out && pair0 >= 0 && npair > 0 && B > 0 && p >= 0.f && p < 1.f);
     hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3(1024), dim3(256), 0, rlt_stream(stream), seed, pair0, npair, B, p, out);
     return RLT_LAUNCH_RESULT();
-}
-
-// ---- workspace layout of the backward pass: [ delta (S,H,B) floats, padded to 1 KiB | dO tile records (bf16x3) ]
-static size_t delta_bytes(int S, int B, int H) { return ((size_t)S * H * B * sizeof(float) + 1023) / 1024 * 1024; }
-// bf16x6 at head dim 16, 512 lists and more: the pipelined backward kernels of attention6n.hip stage pre-split tile images of
-// Q, K, V, dO and the rows' seeds from the workspace (behind delta): dO + seeds are written by _bwd_prepare, Q by _bwd_dkv,
-// K / V by _bwd_dq - each part prepares what it reads, so the three entry points stay callable on their own.  RLT_A6N_IMG=0:
-// the two-wavefront kernels (A/B runs).  Train-mode launches (drop_p > 0) do not use the images.
-static bool a6n_images(int HD, int B) {
-    static const bool on = [] {
-        for (const char* v : {"RLT_A6N", "RLT_A6N_1", "RLT_A6N_IMG"}) { const char* e = getenv(v); if (e && atoi(e) == 0) return false; }
-        return true;
-    }();
-    return on && HD == 16 && B >= 512 && attn6_use(HD, 0.f) && !attn6_img(HD);
-}
-
-// bf16x6 at head dim 16, 512 lists and more in whole 128-row tiles, no dropout: the pipelined forward kernel of attention6n.hip stages
-// pre-split K / V tile images (written by two prepare passes of the call) and leaves a flag word per workgroup for the fix-up
-// launch - both in the forward's `images` buffer (K images | V images | flags).
-// RLT_A6N_F1=0: the two-wavefront kernel (A/B runs)
-static bool a6n_fwd_images(int HD, int B) {
-    static const bool on = [] { const char* e = getenv("RLT_A6N_F1"); return !e || atoi(e) != 0; }();
-    return on && a6n_images(HD, B) && B % 128 == 0;
-}
-static size_t a6n_flags_bytes(int S, int B, int H) { return ((size_t)S * H * rlt_cdiv(B, 256) * sizeof(uint32_t) + 255) / 256 * 256; }
-
-// bf16x6 at head dim 64, 512 lists and more in whole 64-row tiles, with or without dropout: the pipelined forward kernel of attention6h.hip, same
-// scheme - K / V tile images of the call + a flag word per 256-query workgroup in the forward's `images` buffer, fix-up launch of
-// attention6.hip's ping-pong kernel for the flagged workgroups.  RLT_A6H=0: attention6.hip's kernel alone (A/B runs)
-static bool a6h_fwd_images(int HD, int B) {
-    static const bool on = [] { const char* e = getenv("RLT_A6H"); return !e || atoi(e) != 0; }();
-    return on && HD == 64 && B >= 512 && B % 64 == 0 && attn6_use(HD, 0.f) && !attn6_img(HD);
-}
-
-size_t rlt_list_attention_fwd_workspace(int S, int B, int H, int HD, float drop_p, int precision) {
-    RLT_PREC_SCOPE_SZ(precision);
-    if (S <= 0 || B <= 0 || H <= 0) return 0;
-    if (!hd_ok(HD)) return 0;
-    if (attn_mode(HD) == 1) return rlt_attn3_images_bytes(S, B, H, HD, 3);
-    // (the pipelined forward kernels have no train-mode form: a call with dropout does not use - and need not be given - their images)
-    if (!(drop_p > 0.f) && a6n_fwd_images(HD, B)) return rlt_attn6n_fwd_images_bytes(S, B, H) + a6n_flags_bytes(S, B, H);
-    if (a6h_fwd_images(HD, B)) return rlt_attn6h_fwd_images_bytes(S, B, H) + a6n_flags_bytes(S, B, H);       // (train mode included)
-    return attn6_img(HD) ? rlt_attn6_images_bytes(S, B, H, HD, 3) : 0;
-}
-
-// 1: the backward entry points read the forward's `images` (split-bf16 tile records; the RLT_ATTN6_IMG staging) - the caller keeps
-// the buffer until the backward pass; 0: `images` is scratch of the forward call (the pipelined bf16x6 forward kernels) or empty
-int rlt_list_attention_images_retained(int S, int B, int H, int HD, int precision) {
-    RLT_PREC_SCOPE_SZ(precision);
-    if (S <= 0 || B <= 0 || H <= 0 || !hd_ok(HD)) return 0;
-    return attn_mode(HD) == 1 || attn6_img(HD) ? 1 : 0;
-}
-
-int rlt_list_attention_fwd(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed,
-                           float* out, float* lse, void* images, size_t images_bytes, int precision, void* stream) {
-    RLT_PREC_SCOPE(precision);
-    RLT_CHECK_ARG(qkv && out && lse && S > 0 && B > 0 && H > 0 && drop_p >= 0.f && drop_p < 1.f);
-    RLT_CHECK_SHAPE(hd_ok(HD));
-    if (!(rlt_aligned16(qkv) && rlt_aligned16(out))) return RLT_E_ALIGN;
-    AttnArgs a{};
-    a.qkv = qkv; a.o = out; a.lse_o = lse; a.S = S; a.B = B; a.H = H;
-    a.scale = 1.0f / sqrtf((float)HD);
-    a.drop_p = drop_p; a.drop_thr = rlt_drop_threshold(drop_p); a.seed = seed;
-    hipStream_t st = rlt_stream(stream);
-    if (attn_mode(HD) == 1 && images) {      // split-bf16: needs room for the Q/K/V tile records
-        if (images_bytes < rlt_attn3_images_bytes(S, B, H, HD, 3)) return RLT_E_WORKSPACE;
-        if (!rlt_aligned16(images)) return RLT_E_ALIGN;
-        return rlt_attn3_run(0, a, HD, images, nullptr, st);
-    }
-    if (attn6_use(HD, drop_p)) {
-        if (drop_p <= 0.f && a6n_fwd_images(HD, B) && images && rlt_aligned16(images) &&
-            images_bytes >= rlt_attn6n_fwd_images_bytes(S, B, H) + a6n_flags_bytes(S, B, H)) {
-            a.img = images;
-            a.redo = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(images) + rlt_attn6n_fwd_images_bytes(S, B, H));
-            int rc = rlt_attn6n_prepare_at(1, 0, a, st);          // K, V tile images of this call
-            if (!rc) rc = rlt_attn6n_prepare_at(2, 1, a, st);
-            if (rc) return rc;
-            return rlt_attn6n_run(0, a, st);
-        }
-        if (a6h_fwd_images(HD, B) && images && rlt_aligned16(images) &&
-            images_bytes >= rlt_attn6h_fwd_images_bytes(S, B, H) + a6n_flags_bytes(S, B, H)) {
-            AttnArgs b = a;
-            b.img = images;
-            b.redo = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(images) + rlt_attn6h_fwd_images_bytes(S, B, H));
-            int rc = rlt_attn6h_prepare2(1, 0, 2, 1, b, st);        // K, V tile images of this call
-            if (!rc) rc = rlt_attn6h_run(0, b, st);
-            if (rc) return rc;
-            b.img = nullptr;                                        // the fix-up launch stages its tiles itself
-            return rlt_attn6_run(0, b, HD, st);
-        }
-        if (attn6_img(HD) && images) {       // the backward kernels will stage from these images: they must all be written
-            if (images_bytes < rlt_attn6_images_bytes(S, B, H, HD, 3)) return RLT_E_WORKSPACE;
-            if (!rlt_aligned16(images)) return RLT_E_ALIGN;
-            a.img = images;
-            const int rc = rlt_attn6_run(3, a, HD, st);          // Q / K / V tile images (Q for the backward pass)
-            if (rc) return rc;
-        }
-        return rlt_attn6_run(0, a, HD, st);
-    }
-    if (HD == 128) return launch_fwd<128>(a, st);
-    if (HD == 64) return launch_fwd<64>(a, st);
-    if (HD == 32) return launch_fwd<32>(a, st);
-    if (attn16_use()) return rlt_attn16_run(0, a, st);
-    return launch_fwd<16>(a, st);
-}
-
-// bytes behind delta: the dO tile records (split-bf16), the dO images (RLT_ATTN6_IMG) or the four image blocks + seeds of the pipelined
-// head-dim-16 kernels (no dropout only: the train-mode kernels stage their tiles themselves)
-static size_t bwd_ws_extra(int S, int B, int H, int HD, float drop_p) {
-    return attn_mode(HD) == 1 ? rlt_attn3_images_bytes(S, B, H, HD, 1)
-         : attn6_img(HD) ? rlt_attn6_images_bytes(S, B, H, HD, 1)
-         : a6n_images(HD, B) && !(drop_p > 0.f) ? rlt_attn6n_images_bytes(S, B, H) : 0;
-}
-size_t rlt_list_attention_bwd_workspace(int S, int B, int H, int HD, float drop_p, int precision) {
-    RLT_PREC_SCOPE_SZ(precision);
-    if (S <= 0 || B <= 0 || H <= 0) return 0;
-    if (!hd_ok(HD)) return 0;
-    return delta_bytes(S, B, H) + bwd_ws_extra(S, B, H, HD, drop_p);
-}
-
-static int bwd_prepare(const float* out, const float* dout, const float* lse, int S, int B, int H, int HD,
-                       const void* images, void* ws, size_t ws_bytes, float drop_p, void* stream) {
-    RLT_CHECK_ARG(out && dout && lse && ws && S > 0 && B > 0 && H > 0 && drop_p >= 0.f && drop_p < 1.f);
-    RLT_CHECK_SHAPE(hd_ok(HD));
-    const bool split = attn_mode(HD) == 1 && images;
-    const bool img6 = !split && attn6_img(HD) && images;      // bwd_part hands ws + delta to the kernels as the dO images
-    const bool img6n = !split && a6n_images(HD, B) && drop_p <= 0.f;
-    if (ws_bytes < delta_bytes(S, B, H) + (split ? rlt_attn3_images_bytes(S, B, H, HD, 1)
-                                                 : img6 ? rlt_attn6_images_bytes(S, B, H, HD, 1)
-                                                 : img6n ? rlt_attn6n_images_bytes(S, B, H) : 0)) return RLT_E_WORKSPACE;
-    if (!rlt_aligned16(ws)) return RLT_E_ALIGN;
-    hipStream_t st = rlt_stream(stream);
-    const size_t T = (size_t)S * B;
-    const int dgrid = (int)((T + 3) / 4 > 4096 ? 4096 : (T + 3) / 4);
-    if (!split) {
-        hipLaunchKernelGGL(attn_delta_kernel, dim3(dgrid), dim3(256), 0, st, out, dout, S, B, H, HD, (float*)ws);
-        int rc = RLT_LAUNCH_RESULT();
-        if (!rc && img6) {
-            AttnArgs a{};                                         // bf16x6 mode: the dO tile images behind delta
-            a.dout = dout; a.S = S; a.B = B; a.H = H;
-            a.dimg = (uint8_t*)ws + delta_bytes(S, B, H);
-            rc = rlt_attn6_run(4, a, HD, st);
-        }
-        if (!rc && img6n) {                                       // head dim 16: the dO tile images and the rows' seeds (-lse, -delta)
-            AttnArgs a{};
-            a.dout = dout; a.lse = lse; a.delta = (const float*)ws; a.S = S; a.B = B; a.H = H;
-            a.img = (uint8_t*)ws + delta_bytes(S, B, H);
-            rc = rlt_attn6n_prepare(3, a, st);
-            if (!rc) rc = rlt_attn6n_prepare(4, a, st);
-        }
-        return rc;
-    }
-    AttnArgs a{};       // split-bf16 mode: the pass that writes the dO records computes delta from the tiles it has in registers
-    a.dout = dout; a.lse = lse; a.delta = (const float*)ws; a.S = S; a.B = B; a.H = H;
-    a.o = const_cast<float*>(out);
-    a.drop_p = drop_p;
-    return rlt_attn3_run(3, a, HD, nullptr, (uint8_t*)ws + delta_bytes(S, B, H), st);
-}
-
-int rlt_list_attention_bwd_prepare(const float* out, const float* dout, const float* lse, int S, int B, int H, int HD, float drop_p,
-                                   const void* images, void* ws, size_t ws_bytes, int precision, void* stream) {
-    RLT_PREC_SCOPE(precision);
-    return bwd_prepare(out, dout, lse, S, B, H, HD, images, ws, ws_bytes, drop_p, stream);
-}
-
-static int bwd_part(int which, const float* qkv, const float* dout, const float* lse, const void* images, void* ws, size_t ws_bytes,
-                    int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, void* stream) {
-    RLT_CHECK_ARG(qkv && dout && lse && ws && dqkv && S > 0 && B > 0 && H > 0 && drop_p >= 0.f && drop_p < 1.f);
-    RLT_CHECK_SHAPE(hd_ok(HD));
-    if (!(rlt_aligned16(qkv) && rlt_aligned16(dout) && rlt_aligned16(dqkv) && rlt_aligned16(ws))) return RLT_E_ALIGN;
-    // the part reads delta - and, by mode, reads or WRITES tile images behind it: the same size rule as _bwd_prepare, evaluated in THIS
-    // call's precision scope (a workspace sized under another mode, or by an older delta-only rule, is refused instead of overrun)
-    if (ws_bytes < delta_bytes(S, B, H) + (images || attn_mode(HD) != 1 ? bwd_ws_extra(S, B, H, HD, drop_p) : 0)) return RLT_E_WORKSPACE;
-    const AttnArgs a = bwd_args(qkv, dout, lse, (const float*)ws, S, B, H, HD, drop_p, seed, dqkv);
-    hipStream_t st = rlt_stream(stream);
-    if (attn_mode(HD) == 1 && images)
-        return rlt_attn3_run(which, a, HD, const_cast<void*>(images), (uint8_t*)ws + delta_bytes(S, B, H), st);
-    if (attn6_use(HD, drop_p)) {
-        AttnArgs b = a;
-        if (attn6_img(HD) && images) {                            // (forward wrote the Q / K / V images, bwd_prepare the dO images)
-            b.img = images;
-            b.dimg = (const uint8_t*)ws + delta_bytes(S, B, H);
-        }
-        if (a6n_images(HD, B) && drop_p == 0.f) {                 // the pipelined head-dim-16 kernels: this part's own images first
-            b.img = (const uint8_t*)ws + delta_bytes(S, B, H);    // (the workspace is scratch: dO images + seeds are there already)
-            int rc = 0;
-            if (which == 1) rc = rlt_attn6n_prepare(0, b, st);                       // dK+dV stages Q (and dO)
-            else { rc = rlt_attn6n_prepare(1, b, st); if (!rc) rc = rlt_attn6n_prepare(2, b, st); }     // dQ stages K and V
-            return rc ? rc : rlt_attn6n_run(which, b, st);
-        }
-        return rlt_attn6_run(which, b, HD, st);
-    }
-    if (HD == 16 && attn16_use()) return rlt_attn16_run(which, a, st);
-    if (which == 1) {
-        if (HD == 128) return launch_dkv<128>(a, st);
-        if (HD == 64) return launch_dkv<64>(a, st);
-        if (HD == 32) return launch_dkv<32>(a, st);
-        return launch_dkv<16>(a, st);
-    }
-    if (HD == 128) return launch_dq<128>(a, st);
-    if (HD == 64) return launch_dq<64>(a, st);
-    if (HD == 32) return launch_dq<32>(a, st);
-    return launch_dq<16>(a, st);
-}
-
-int rlt_list_attention_bwd_dkv(const float* qkv, const float* dout, const float* lse, const void* images, void* ws, size_t ws_bytes,
-                               int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, int precision, void* stream) {
-    RLT_PREC_SCOPE(precision);
-    return bwd_part(1, qkv, dout, lse, images, ws, ws_bytes, S, B, H, HD, drop_p, seed, dqkv, stream);
-}
-
-int rlt_list_attention_bwd_dq(const float* qkv, const float* dout, const float* lse, const void* images, void* ws, size_t ws_bytes,
-                              int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, int precision, void* stream) {
-    RLT_PREC_SCOPE(precision);
-    return bwd_part(2, qkv, dout, lse, images, ws, ws_bytes, S, B, H, HD, drop_p, seed, dqkv, stream);
-}
-
-int rlt_list_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
-                           int S, int B, int H, int HD, float drop_p, uint32_t seed, const void* images, float* dqkv,
-                           void* ws, size_t ws_bytes, int precision, void* stream) {
-    RLT_PREC_SCOPE(precision);
-    RLT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
-    int rc = bwd_prepare(out, dout, lse, S, B, H, HD, images, ws, ws_bytes, drop_p, stream);     // knows whether dO^T is needed
-    if (!rc) rc = rlt_list_attention_bwd_dkv(qkv, dout, lse, images, ws, ws_bytes, S, B, H, HD, drop_p, seed, dqkv, RLT_PRECISION_DEFAULT, stream);
-    if (!rc) rc = rlt_list_attention_bwd_dq(qkv, dout, lse, images, ws, ws_bytes, S, B, H, HD, drop_p, seed, dqkv, RLT_PRECISION_DEFAULT, stream);
-    return rc;
 }
 
 }  // extern "C"

@@ -1403,37 +1403,40 @@ __global__ __launch_bounds__(256, 2) void attn6_bwd_dq_kernel(AttnArgs a) {
 
 }  // namespace
 
+// IMG: the _IMG kernel codes.  The one-wavefront dK+dV / dQ kernels and the ping-pong forward exist at head dim 64 only.
 template <int HD, bool DROP, bool IMG>
-static int attn6_launch(int which, const AttnArgs& a, hipStream_t st) {
+static int attn6_launch(int kernel, int which, const AttnArgs& a, hipStream_t st) {
     const int grid = a.S * a.H * rlt_cdiv(a.B, QT);
     const size_t shm = (size_t)2 * img6<HD>() * sizeof(uint16_t) + (which == 1 ? 2 * KT * sizeof(float) : 0) + KT * sizeof(uint32_t);
     int rc;
-    static const bool pp = [] { const char* e = getenv("RLT_A6_PP"); return !e || atoi(e) != 0; }();    // RLT_A6_PP=0: the two-workgroup form
-    if constexpr (HD == 64) {                 // ping-pong form (instantiated for head dim 64 only): one 512-thread workgroup per CU, 256 queries
-        if (which == 0 && (pp || a.redo)) {          // (a.redo: the fix-up launch behind attention6h.hip's forward is this kernel's grid)
+    if (kernel == RLT_ATTN_X6_PP || kernel == RLT_ATTN_X6_PP_IMG) {     // one 512-thread workgroup per CU, 256 queries
+        if constexpr (HD == 64) {
+            RLT_CHECK_ARG(which == 0);
             const size_t shm_pp = (size_t)4 * img6<HD>() * sizeof(uint16_t) + 2 * KT * sizeof(uint32_t);
             if ((rc = rlt_allow_lds(attn6_fwd_pp_kernel<HD, DROP, IMG>, shm_pp))) return rc;
             hipLaunchKernelGGL((attn6_fwd_pp_kernel<HD, DROP, IMG>), dim3(a.S * a.H * rlt_cdiv(a.B, QT_PP)), dim3(512), shm_pp, st, a);
             return RLT_LAUNCH_RESULT();
         }
+        return RLT_E_ARG;
     }
-    if constexpr (HD == 64) {                 // dK+dV with one wavefront per SIMD: 256 keys per workgroup, double-buffered tiles
-        static const bool dkv1 = [] { const char* e = getenv("RLT_A6_DKV1"); return !e || atoi(e) != 0; }();
-        static const bool dq1 = [] { const char* e = getenv("RLT_A6_DQ1"); return !e || atoi(e) != 0; }();
-        const bool small24 = (long long)a.B * 3 * a.H * HD < (1ll << 24);     // their loaders form B * ld in 24-bit multiplies
-        if (which == 2 && dq1 && small24) {
-            const size_t shm1 = (size_t)4 * IMG1 * sizeof(uint16_t) + 2 * KT * sizeof(uint32_t) + (size_t)4 * 2 * 4 * 64 * sizeof(uint4);
-            if ((rc = rlt_allow_lds(attn6_bwd_dq1_kernel<DROP>, shm1))) return rc;
-            hipLaunchKernelGGL((attn6_bwd_dq1_kernel<DROP>), dim3(a.S * a.H * rlt_cdiv(a.B, QT1)), dim3(256), shm1, st, a);
+    if (kernel == RLT_ATTN_X6_DQ1 || kernel == RLT_ATTN_X6_DKV1) {      // 256 rows per workgroup, double-buffered tiles
+        if constexpr (HD == 64) {
+            RLT_CHECK_ARG((long long)a.B * 3 * a.H * HD < (1ll << 24));  // their loaders form B * ld in 24-bit multiplies
+            RLT_CHECK_ARG(which == (kernel == RLT_ATTN_X6_DQ1 ? 2 : 1));
+            if (which == 2) {
+                const size_t shm1 = (size_t)4 * IMG1 * sizeof(uint16_t) + 2 * KT * sizeof(uint32_t) + (size_t)4 * 2 * 4 * 64 * sizeof(uint4);
+                if ((rc = rlt_allow_lds(attn6_bwd_dq1_kernel<DROP>, shm1))) return rc;
+                hipLaunchKernelGGL((attn6_bwd_dq1_kernel<DROP>), dim3(a.S * a.H * rlt_cdiv(a.B, QT1)), dim3(256), shm1, st, a);
+            } else {
+                const size_t shm1 = (size_t)4 * IMG1 * sizeof(uint16_t) + 2 * 3 * KT * sizeof(float) + (size_t)4 * 2 * 4 * 64 * sizeof(uint4);
+                if ((rc = rlt_allow_lds(attn6_bwd_dkv1_kernel<DROP>, shm1))) return rc;
+                hipLaunchKernelGGL((attn6_bwd_dkv1_kernel<DROP>), dim3(a.S * a.H * rlt_cdiv(a.B, QT1)), dim3(256), shm1, st, a);
+            }
             return RLT_LAUNCH_RESULT();
         }
-        if (which == 1 && dkv1 && small24) {
-            const size_t shm1 = (size_t)4 * IMG1 * sizeof(uint16_t) + 2 * 3 * KT * sizeof(float) + (size_t)4 * 2 * 4 * 64 * sizeof(uint4);
-            if ((rc = rlt_allow_lds(attn6_bwd_dkv1_kernel<DROP>, shm1))) return rc;
-            hipLaunchKernelGGL((attn6_bwd_dkv1_kernel<DROP>), dim3(a.S * a.H * rlt_cdiv(a.B, QT1)), dim3(256), shm1, st, a);
-            return RLT_LAUNCH_RESULT();
-        }
+        return RLT_E_ARG;
     }
+    RLT_CHECK_ARG(!a.redo);                   // (only the ping-pong kernel is a fix-up launch)
     if (which == 0) {
         if ((rc = rlt_allow_lds(attn6_fwd_kernel<HD, DROP, IMG>, shm))) return rc;
         hipLaunchKernelGGL((attn6_fwd_kernel<HD, DROP, IMG>), dim3(grid), dim3(256), shm, st, a);
@@ -1447,9 +1450,9 @@ static int attn6_launch(int which, const AttnArgs& a, hipStream_t st) {
     return RLT_LAUNCH_RESULT();
 }
 template <int HD>
-static int attn6_prepare(int which, const AttnArgs& a, hipStream_t st) {
+static int attn6_prepare(bool dO, const AttnArgs& a, hipStream_t st) {
     const int npair = a.S * a.H, ntile = rlt_cdiv(a.B, KT), E = a.H * HD;
-    if (which == 3)        // Q, K, V images from the packed qkv rows (column blocks 0, E, 2E)
+    if (!dO)               // Q, K, V images from the packed qkv rows (column blocks 0, E, 2E)
         hipLaunchKernelGGL((attn6_prepare_kernel<HD>), dim3(npair * ntile, 3), dim3(256), 0, st, a.qkv, (size_t)3 * E, 0, E, a.S, a.B, a.H,
                            (uint8_t*)const_cast<void*>(a.img));
     else                   // dO images
@@ -1458,10 +1461,12 @@ static int attn6_prepare(int which, const AttnArgs& a, hipStream_t st) {
     return RLT_LAUNCH_RESULT();
 }
 template <int HD, bool DROP>
-static int attn6_dispatch(int which, const AttnArgs& a, hipStream_t st) {
-    if (which >= 3) return attn6_prepare<HD>(which, a, st);
-    const bool img = a.img != nullptr && (which != 1 || a.dimg != nullptr);
-    return img ? attn6_launch<HD, DROP, true>(which, a, st) : attn6_launch<HD, DROP, false>(which, a, st);
+static int attn6_dispatch(int kernel, int which, const AttnArgs& a, hipStream_t st) {
+    if (kernel == RLT_ATTN_X6_IMG || kernel == RLT_ATTN_X6_PP_IMG) {
+        RLT_CHECK_ARG(a.img && (which != 1 || a.dimg));
+        return attn6_launch<HD, DROP, true>(kernel, which, a, st);
+    }
+    return attn6_launch<HD, DROP, false>(kernel, which, a, st);
 }
 
 size_t rlt_attn6_images_bytes(int S, int B, int H, int HD, int nmat) {
@@ -1480,15 +1485,21 @@ extern "C" int rlt_debug_pp_stamps(unsigned long long* out) {
 }
 #endif
 
-// which: 0 forward, 1 dK/dV, 2 dQ, 3 / 4 the prepare passes; head dim 16, 32 or 64 (the caller checks).  Dropout is a template
+int rlt_attn6_prepare(bool dO, const AttnArgs& a, int HD, hipStream_t st) {
+    RLT_CHECK_ARG(dO ? a.dout && a.dimg : a.qkv && a.img);
+    if (HD == 64) return attn6_prepare<64>(dO, a, st);
+    if (HD == 32) return attn6_prepare<32>(dO, a, st);
+    if (HD == 16) return attn6_prepare<16>(dO, a, st);
+    return RLT_E_ARG;
+}
+
+// kernel: one of the RLT_ATTN_X6* codes of this file; which: 0 forward, 1 dK/dV, 2 dQ; head dim 16, 32 or 64.  Dropout is a template
 // parameter: hipcc if-converts a run-time `drop_p > 0` test and executes the hashes regardless.
-int rlt_attn6_run(int which, const AttnArgs& a, int HD, hipStream_t st) {
+int rlt_attn6_run(int kernel, int which, const AttnArgs& a, int HD, hipStream_t st) {
+    RLT_CHECK_ARG(kernel >= RLT_ATTN_X6 && kernel <= RLT_ATTN_X6_DQ1 && which >= 0 && which <= 2);
     const bool drop = a.drop_p > 0.f;
-    if (HD == 64) return drop ? attn6_dispatch<64, true>(which, a, st) : attn6_dispatch<64, false>(which, a, st);
-    if (HD == 32) return drop ? attn6_dispatch<32, true>(which, a, st) : attn6_dispatch<32, false>(which, a, st);
-    // head dim 16: the 16x16x32 kernels of attention6n.hip (RLT_A6N=0: the 32x32x16 kernels of this file, A/B runs; the
-    // pre-split-image staging exists in this file only)
-    static const bool a6n = [] { const char* e = getenv("RLT_A6N"); return !e || atoi(e) != 0; }();
-    if (a6n && which < 3 && !(a.img != nullptr && (which != 1 || a.dimg != nullptr))) return rlt_attn6n_run(which, a, st);
-    return drop ? attn6_dispatch<16, true>(which, a, st) : attn6_dispatch<16, false>(which, a, st);
+    if (HD == 64) return drop ? attn6_dispatch<64, true>(kernel, which, a, st) : attn6_dispatch<64, false>(kernel, which, a, st);
+    if (HD == 32) return drop ? attn6_dispatch<32, true>(kernel, which, a, st) : attn6_dispatch<32, false>(kernel, which, a, st);
+    if (HD == 16) return drop ? attn6_dispatch<16, true>(kernel, which, a, st) : attn6_dispatch<16, false>(kernel, which, a, st);
+    return RLT_E_ARG;
 }

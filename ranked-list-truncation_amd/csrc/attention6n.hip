@@ -1122,16 +1122,20 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs
 }
 
 template <bool DROP>
-int launch6n(int which, const AttnArgs& a, hipStream_t st) {
+int launch6n(int kernel, int which, const AttnArgs& a, hipStream_t st) {
     constexpr int NB = RLT_A6N_NB, NBK = RLT_A6N_NBK;
     const size_t shm = (size_t)4 * IMGN * sizeof(uint16_t) + (which == 1 ? 2 * 3 * KT * sizeof(float) : 2 * KT * sizeof(uint32_t));
-    // backward without dropout at 512 lists and more: the one-wavefront pipelined kernels (RLT_A6N_1=0: the kernels above, A/B runs)
-    static const bool one = [] { const char* e = getenv("RLT_A6N_1"); return !e || atoi(e) != 0; }();
-    if (!DROP && one && which != 0 && a.B >= 512 && a.img) {
+    const dim3 gq(a.S * a.H * rlt_cdiv(a.B, 64 * NB)), gk(a.S * a.H * rlt_cdiv(a.B, 64 * NBK));
+    if (kernel == RLT_ATTN_X6N_PIPE) {        // the one-wavefront pipelined kernels: no dropout, 512 lists and more, images in a.img
+        RLT_CHECK_ARG(!DROP && a.B >= 512 && a.img);
         const size_t shm1 = (size_t)4 * IMGT * sizeof(uint16_t) + (which == 1 ? 2 * 2 * KTN1 * sizeof(float) : 0);
         const dim3 grid1(a.S * a.H * rlt_cdiv(a.B, 256));
         int rc;
-        if (which == 1) {
+        if (which == 0) {                     // whole 128-row tiles, K / V images and a flag word per workgroup (a.redo) for the fix-up launch
+            RLT_CHECK_ARG(a.B % KTN1 == 0 && a.redo && NB == 4);
+            if ((rc = rlt_allow_lds(attn6n_fwd1_kernel, shm1))) return rc;
+            hipLaunchKernelGGL(attn6n_fwd1_kernel, gq, dim3(256), shm1, st, a);
+        } else if (which == 1) {
             if ((rc = rlt_allow_lds(attn6n_bwd1_kernel<true>, shm1))) return rc;
             hipLaunchKernelGGL((attn6n_bwd1_kernel<true>), grid1, dim3(256), shm1, st, a);
         } else {
@@ -1140,19 +1144,9 @@ int launch6n(int which, const AttnArgs& a, hipStream_t st) {
         }
         return RLT_LAUNCH_RESULT();
     }
-    const bool seed = a.B >= 512;
-    const dim3 gq(a.S * a.H * rlt_cdiv(a.B, 64 * NB)), gk(a.S * a.H * rlt_cdiv(a.B, 64 * NBK));
-    // forward without dropout, 512 lists and more in whole 128-row tiles, K / V images prepared (a.img) and a flag word per workgroup
-    // (a.redo): the pipelined kernel, then the two-wavefront kernel for the workgroups it flagged (RLT_A6N_F1=0: the latter alone)
-    static const bool fwd1 = [] { const char* e = getenv("RLT_A6N_F1"); return !e || atoi(e) != 0; }();
-    if (!DROP && one && fwd1 && which == 0 && a.B >= 512 && a.B % KTN1 == 0 && a.img && a.redo && NB == 4) {
-        const size_t shm1 = (size_t)4 * IMGT * sizeof(uint16_t);
-        const int rc = rlt_allow_lds(attn6n_fwd1_kernel, shm1);
-        if (rc) return rc;
-        hipLaunchKernelGGL(attn6n_fwd1_kernel, gq, dim3(256), shm1, st, a);
-        hipLaunchKernelGGL((attn6n_fwd_kernel<NB, DROP, true>), gq, dim3(256), shm, st, a);
-        return RLT_LAUNCH_RESULT();
-    }
+    // the two-wavefront kernels: the seeded form is the one for 512 lists and more; a.redo makes the forward a fix-up launch
+    const bool seed = kernel == RLT_ATTN_X6N_2W_SEEDED;
+    RLT_CHECK_ARG(seed == (a.B >= 512) && (!a.redo || (which == 0 && seed)));
     if (which == 0) {
         if (seed) hipLaunchKernelGGL((attn6n_fwd_kernel<NB, DROP, true>), gq, dim3(256), shm, st, a);
         else hipLaunchKernelGGL((attn6n_fwd_kernel<NB, DROP, false>), gq, dim3(256), shm, st, a);
@@ -1198,7 +1192,8 @@ int rlt_attn6n_prepare_at(int what, int slot, const AttnArgs& a, hipStream_t st)
     return RLT_LAUNCH_RESULT();
 }
 
-// which = 0 forward, 1 dK/dV, 2 dQ (head dim 16, bf16x6 arithmetic)
-int rlt_attn6n_run(int which, const AttnArgs& a, hipStream_t st) {
-    return a.drop_p > 0.f ? launch6n<true>(which, a, st) : launch6n<false>(which, a, st);
+// kernel: RLT_ATTN_X6N_2W, _X6N_2W_SEEDED or _X6N_PIPE; which = 0 forward, 1 dK/dV, 2 dQ (head dim 16, bf16x6 arithmetic)
+int rlt_attn6n_run(int kernel, int which, const AttnArgs& a, hipStream_t st) {
+    RLT_CHECK_ARG(kernel >= RLT_ATTN_X6N_2W && kernel <= RLT_ATTN_X6N_PIPE && which >= 0 && which <= 2);
+    return a.drop_p > 0.f ? launch6n<true>(kernel, which, a, st) : launch6n<false>(kernel, which, a, st);
 }

@@ -87,6 +87,7 @@ _SIGNATURES = {
     "rlt_list_attention_bwd_prepare": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, c_size_t, c_int, P]),
     "rlt_list_attention_bwd_dkv": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
     "rlt_list_attention_bwd_dq": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
+    "rlt_list_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
     "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
@@ -160,6 +161,36 @@ def gemm_last_dispatch():
     check(load().rlt_gemm_last_dispatch(ctypes.byref(d)), "rlt_gemm_last_dispatch")
     out = {f: int(getattr(d, f)) for f in GEMM_DISPATCH_FIELDS}
     out["family"] = GEMM_FAMILIES[out["family"]]
+    return out
+
+
+ATTN_KERNELS = ("none", "f32", "f32_sb", "f32_occ1", "f32_hd16", "x3", "x6", "x6_img", "x6_pp", "x6_pp_img", "x6_dkv1", "x6_dq1",
+                "x6n_2w", "x6n_2w_seeded", "x6n_pipe", "x6h_pipe")                  # RLT_ATTN_NONE .. RLT_ATTN_X6H_PIPE
+ATTN_PREPARE = ("q", "k", "v", "do", "seeds", "delta")                              # bits of RLT_ATTN_PREP_*
+ATTN_IMAGES = ("none", "x3_qkv", "x6_qkv", "x6n_kv", "x6h_kv")                      # RLT_ATTN_IMAGES_*
+ATTN_WS = ("delta", "x3_do", "x6_do", "x6n_blocks")                                 # RLT_ATTN_WS_*
+ATTN_PLAN_INTS = ("fwd", "fwd_fixup", "dkv", "dq", "fwd_prepare", "bwd_prepare", "dkv_prepare", "dq_prepare",
+                  "images_kind", "images_retained", "ws_kind")
+ATTN_PLAN_SIZES = ("images_bytes", "flags_offset", "flags_bytes", "delta_bytes", "ws_extra_bytes", "ws_bytes",
+                   "ws_prepare_bytes", "ws_part_bytes")
+
+
+class AttentionPlan(ctypes.Structure):
+    """rlt_attention_plan: what the list-attention entry points decide for one call."""
+    _fields_ = [(f, c_int) for f in ATTN_PLAN_INTS] + [(f, c_size_t) for f in ATTN_PLAN_SIZES]
+
+
+def attention_plan(S, B, H, HD, drop_p, have_images, precision=PRECISION_DEFAULT):
+    """-> dict of the plan's fields: kernels, image / workspace kinds as their names, prepare masks as tuples of ATTN_PREPARE names."""
+    d = AttentionPlan()
+    check(load().rlt_list_attention_plan(S, B, H, HD, drop_p, int(bool(have_images)), precision, ctypes.byref(d)), "rlt_list_attention_plan")
+    out = {f: int(getattr(d, f)) for f in ATTN_PLAN_INTS + ATTN_PLAN_SIZES}
+    for f in ("fwd", "fwd_fixup", "dkv", "dq"):
+        out[f] = ATTN_KERNELS[out[f]]
+    for f in ("fwd_prepare", "bwd_prepare", "dkv_prepare", "dq_prepare"):
+        out[f] = tuple(n for i, n in enumerate(ATTN_PREPARE) if out[f] >> i & 1)
+    out["images_kind"] = ATTN_IMAGES[out["images_kind"]]
+    out["ws_kind"] = ATTN_WS[out["ws_kind"]]
     return out
 
 
