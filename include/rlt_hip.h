@@ -482,6 +482,20 @@ int rlt_bilstm_rec_fwd_x(const float* x, int I, const float* w_ih_fwd, const flo
                          float* gates, float* h_out, float* c_out, int precision, void* stream);
 int rlt_bilstm_rec_bwd(float* gates, const float* c, const float* w_hh_fwd, const float* w_hh_rev,
                        const float* d_hout, int S, int B, int precision, void* stream);
+/* What the three entry points above decide for one call (csrc/lstm_common.h: the decision is taken once per call, there; tests:
+ * tests/test_lstm_plan.py, tests/test_lstm_dispatch_gpu.py).  Host only: no device work, no influence on the choice.
+ * xin: 1 for rlt_bilstm_rec_fwd_x (the forward kernel's instantiation with the fused input projection), 0 for
+ * rlt_bilstm_rec_fwd; the codes do not depend on it.  Errors: RLT_E_ARG (out NULL, B <= 0, xin not 0 / 1, precision).
+ *   fwd, bwd               the kernel of the forward / of rlt_bilstm_rec_bwd, an RLT_LSTM_* code
+ *   fwd_lists, bwd_lists   lists per workgroup of that kernel (the grid is ceil(B / lists) x 2 directions)
+ * The struct is named by its tag (C and C++ both allow a function of the same name next to a struct tag, not next to a typedef). */
+#define RLT_LSTM_F32          1   /* bilstm_fwd_kernel / bilstm_bwd_kernel: exact fp32 on the f32 MFMA */
+#define RLT_LSTM_X3           2   /* bilstm3_fwd_kernel / bilstm3_bwd8_kernel: bf16x3 */
+#define RLT_LSTM_X6           3   /* bilstm6_fwd_kernel: bf16x6 in two phases per step (forward only: its backward is RLT_LSTM_F32) */
+#define RLT_LSTM_X6W_SINGLE   4   /* bilstm6w_*_kernel<.., SINGLE>: bf16x6, one wavefront per SIMD, one 16-list half per workgroup */
+#define RLT_LSTM_X6W_HALVES   5   /* bilstm6w_*_kernel: ... two independent 16-list halves per workgroup */
+struct rlt_bilstm_rec_plan { int fwd, bwd, fwd_lists, bwd_lists; };
+int rlt_bilstm_rec_plan(int B, int xin, int precision, struct rlt_bilstm_rec_plan* out);
 
 /* ------------------------------------------------------------------ PATH-LEVEL ENTRY POINTS
  * One call = the forward or the backward of one module of the reference's models, composed inside the library from

@@ -728,19 +728,58 @@ __global__ __launch_bounds__(512) void bilstm6_fwd_kernel(float* __restrict__ ga
 
 }  // namespace
 
+// Every environment switch of the recurrence, read once per process (A/B runs: bench.py, tools/x6_probe.py)
+struct LstmEnv {
+    bool lstm6;         // RLT_LSTM6=0: bf16x6 FORWARD on the f32 MFMA kernels
+    bool lstm6w;        // RLT_LSTM6W=0: round 4's two-phase forward and the f32 MFMA backward instead of lstm6w.hip
+    bool lstm6w_bwd;    // RLT_LSTM6W_BWD=0: the f32 MFMA backward recurrence of rounds 1-4 only
+    bool single;        // RLT_LSTM6W_SINGLE=0: lstm6w.hip always in its two-half form
+};
+static const LstmEnv& lstm_env() {
+    static const LstmEnv env = [] {
+        auto on = [](const char* e) { return !e || atoi(e) != 0; };
+        LstmEnv v;
+        v.lstm6 = on(getenv("RLT_LSTM6"));
+        v.lstm6w = on(getenv("RLT_LSTM6W"));
+        v.lstm6w_bwd = on(getenv("RLT_LSTM6W_BWD"));
+        v.single = on(getenv("RLT_LSTM6W_SINGLE"));
+        return v;
+    }();
+    return env;
+}
+
+LstmPlan lstm_plan(int B) {
+    const LstmEnv& env = lstm_env();
+    const int prec = rlt_precision();
+    // (lstm6w.hip bounds its buffer instructions with 32-bit byte counts of B * 4096: 2^20 lists and more take the kernels of this file)
+    const bool w6_fits = B < (1 << 20);
+    // one 16-list half per workgroup while that still gives every workgroup its own CU (256 CUs, two directions)
+    const int w6 = env.single && B <= 16 * 128 ? RLT_LSTM_X6W_SINGLE : RLT_LSTM_X6W_HALVES;
+    const int w6_lists = w6 == RLT_LSTM_X6W_SINGLE ? 16 : 32;
+    LstmPlan p;
+    p.fwd_lists = p.bwd_lists = LISTS;
+    if (prec == RLT_PRECISION_BF16X6 && env.lstm6 && env.lstm6w && w6_fits) { p.fwd = w6; p.fwd_lists = w6_lists; }
+    else if (prec == RLT_PRECISION_BF16X6 && env.lstm6) p.fwd = RLT_LSTM_X6;
+    else if (prec == RLT_PRECISION_BF16X3) p.fwd = RLT_LSTM_X3;
+    else p.fwd = RLT_LSTM_F32;
+    // (the backward does not read RLT_LSTM6: with it off, bf16x6 still takes lstm6w.hip's backward)
+    if (prec == RLT_PRECISION_BF16X6 && env.lstm6w && env.lstm6w_bwd && w6_fits) { p.bwd = w6; p.bwd_lists = w6_lists; }
+    else if (prec == RLT_PRECISION_BF16X3) p.bwd = RLT_LSTM_X3;
+    else p.bwd = RLT_LSTM_F32;
+    return p;
+}
+
 extern "C" {
 
 static int launch_bilstm_fwd(float* gates, const float* w_hh_fwd, const float* w_hh_rev, int S, int B,
                              float* h_out, float* c_out, const XIn& xi, void* stream) {
-    const dim3 grid(rlt_cdiv(B, LISTS), 2), block(1024);
+    const LstmPlan plan = lstm_plan(B);
+    const dim3 grid(rlt_cdiv(B, plan.fwd_lists), 2), block(1024);
     hipStream_t st = rlt_stream(stream);
-    static const bool lstm6_on = [] { const char* e = getenv("RLT_LSTM6"); return !e || atoi(e) != 0; }();      // RLT_LSTM6=0: the f32 MFMA kernels (A/B runs)
-    static const bool lstm6w_on = [] { const char* e = getenv("RLT_LSTM6W"); return !e || atoi(e) != 0; }();    // RLT_LSTM6W=0: round 4's two-phase kernel
-    // (lstm6w.hip bounds its buffer instructions with 32-bit byte counts of B * 4096: 2^20 lists and more take the kernels of this file)
-    if (rlt_precision() == RLT_PRECISION_BF16X6 && lstm6_on && lstm6w_on && B < (1 << 20)) {
-        const int rc = rlt_lstm6w_fwd(gates, w_hh_fwd, w_hh_rev, S, B, h_out, c_out, xi, stream);
+    if (plan.fwd == RLT_LSTM_X6W_SINGLE || plan.fwd == RLT_LSTM_X6W_HALVES) {
+        const int rc = rlt_lstm6w_fwd(plan.fwd, plan.fwd_lists, gates, w_hh_fwd, w_hh_rev, S, B, h_out, c_out, xi, stream);
         if (rc) return rc;
-    } else if (rlt_precision() == RLT_PRECISION_BF16X6 && lstm6_on) {
+    } else if (plan.fwd == RLT_LSTM_X6) {
         auto go = [&](auto kern) {
             const int rc = rlt_allow_lds(kern, LSTM6_LDS);
             if (rc) return rc;
@@ -751,7 +790,7 @@ static int launch_bilstm_fwd(float* gates, const float* w_hh_fwd, const float* w
         const int rc = xi.x ? (full ? go(bilstm6_fwd_kernel<true, true>) : go(bilstm6_fwd_kernel<true, false>))
                             : (full ? go(bilstm6_fwd_kernel<false, true>) : go(bilstm6_fwd_kernel<false, false>));
         if (rc) return rc;
-    } else if (rlt_precision() == RLT_PRECISION_BF16X3) {
+    } else if (plan.fwd == RLT_LSTM_X3) {
         if (xi.x) hipLaunchKernelGGL(bilstm3_fwd_kernel<true>, grid, block, 0, st, gates, w_hh_fwd, w_hh_rev, S, B, h_out, c_out, xi);
         else hipLaunchKernelGGL(bilstm3_fwd_kernel<false>, grid, block, 0, st, gates, w_hh_fwd, w_hh_rev, S, B, h_out, c_out, xi);
     } else {
@@ -759,6 +798,13 @@ static int launch_bilstm_fwd(float* gates, const float* w_hh_fwd, const float* w
         else hipLaunchKernelGGL(bilstm_fwd_kernel<false>, grid, block, 0, st, gates, w_hh_fwd, w_hh_rev, S, B, h_out, c_out, xi);
     }
     return RLT_LAUNCH_RESULT();
+}
+
+int rlt_bilstm_rec_plan(int B, int xin, int precision, struct rlt_bilstm_rec_plan* out) {
+    RLT_PREC_SCOPE(precision);
+    RLT_CHECK_ARG(out && B > 0 && (xin == 0 || xin == 1));
+    *out = lstm_plan(B);
+    return 0;
 }
 
 int rlt_bilstm_rec_fwd(float* gates, const float* w_hh_fwd, const float* w_hh_rev, int S, int B,
@@ -800,20 +846,15 @@ int rlt_bilstm_rec_bwd(float* gates, const float* c, const float* w_hh_fwd, cons
     int rc = rlt_allow_lds(bilstm_bwd_kernel, shm);
     if (!rc) rc = rlt_allow_lds(bilstm3_bwd8_kernel, shm8);
     if (rc) return rc;
-    static const bool lstm6w_bwd_on = [] {        // RLT_LSTM6W=0 / RLT_LSTM6W_BWD=0: the f32 MFMA backward recurrence of rounds 1-4 (A/B runs)
-        const char* e = getenv("RLT_LSTM6W");
-        const char* b = getenv("RLT_LSTM6W_BWD");
-        return (!e || atoi(e) != 0) && (!b || atoi(b) != 0);
-    }();
-    if (rlt_precision() == RLT_PRECISION_BF16X6 && lstm6w_bwd_on && B < (1 << 20)) {
-        rc = rlt_lstm6w_bwd(gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B, stream);
+    const LstmPlan plan = lstm_plan(B);
+    const dim3 grid(rlt_cdiv(B, plan.bwd_lists), 2);
+    if (plan.bwd == RLT_LSTM_X6W_SINGLE || plan.bwd == RLT_LSTM_X6W_HALVES) {
+        rc = rlt_lstm6w_bwd(plan.bwd, plan.bwd_lists, gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B, stream);
         if (rc) return rc;
-    } else if (rlt_precision() == RLT_PRECISION_BF16X3)
-        hipLaunchKernelGGL(bilstm3_bwd8_kernel, dim3(rlt_cdiv(B, LISTS), 2), dim3(512), shm8, rlt_stream(stream),
-                           gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B);
+    } else if (plan.bwd == RLT_LSTM_X3)
+        hipLaunchKernelGGL(bilstm3_bwd8_kernel, grid, dim3(512), shm8, rlt_stream(stream), gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B);
     else
-        hipLaunchKernelGGL(bilstm_bwd_kernel, dim3(rlt_cdiv(B, LISTS), 2), dim3(1024), shm, rlt_stream(stream),
-                           gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B);
+        hipLaunchKernelGGL(bilstm_bwd_kernel, grid, dim3(1024), shm, rlt_stream(stream), gates, c, w_hh_fwd, w_hh_rev, d_hout, S, B);
     return RLT_LAUNCH_RESULT();
 }
 

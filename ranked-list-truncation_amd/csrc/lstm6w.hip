@@ -604,16 +604,10 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
 
 }  // namespace
 
-// one 16-list half per workgroup while that still gives every workgroup its own CU (256 CUs, two directions)
-static bool w6_single(int B) {
-    static const int on = [] { const char* e = getenv("RLT_LSTM6W_SINGLE"); return e ? atoi(e) : 1; }();      // 0: always two halves (A/B runs)
-    return on && B <= 16 * 128;
-}
-
-int rlt_lstm6w_fwd(float* gates, const float* w_hh_fwd, const float* w_hh_rev, int S, int B, float* h_out, float* c_out,
-                   const RltXIn& xi, void* stream) {
-    const bool single = w6_single(B);
-    const dim3 grid(rlt_cdiv(B, single ? 16 : 32), 2), block(256);
+int rlt_lstm6w_fwd(int kernel, int lists, float* gates, const float* w_hh_fwd, const float* w_hh_rev, int S, int B, float* h_out,
+                   float* c_out, const RltXIn& xi, void* stream) {
+    const bool single = kernel == RLT_LSTM_X6W_SINGLE;
+    const dim3 grid(rlt_cdiv(B, lists), 2), block(256);
     hipStream_t st = rlt_stream(stream);
     auto go = [&](auto kern) {
         const int rc = rlt_allow_lds(kern, W6_LDS);
@@ -625,13 +619,13 @@ int rlt_lstm6w_fwd(float* gates, const float* w_hh_fwd, const float* w_hh_rev, i
     return single ? go(bilstm6w_fwd_kernel<false, true>) : go(bilstm6w_fwd_kernel<false, false>);
 }
 
-int rlt_lstm6w_bwd(float* gates, const float* c, const float* w_hh_fwd, const float* w_hh_rev, const float* d_hout, int S, int B,
-                   void* stream) {
-    const bool single = w6_single(B);
+int rlt_lstm6w_bwd(int kernel, int lists, float* gates, const float* c, const float* w_hh_fwd, const float* w_hh_rev, const float* d_hout,
+                   int S, int B, void* stream) {
+    const bool single = kernel == RLT_LSTM_X6W_SINGLE;
     auto go = [&](auto kern) {
         const int rc = rlt_allow_lds(kern, WB_LDS);
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(rlt_cdiv(B, single ? 16 : 32), 2), dim3(256), WB_LDS, rlt_stream(stream), gates, c, w_hh_fwd, w_hh_rev,
+        hipLaunchKernelGGL(kern, dim3(rlt_cdiv(B, lists), 2), dim3(256), WB_LDS, rlt_stream(stream), gates, c, w_hh_fwd, w_hh_rev,
                            d_hout, S, B);
         return 0;
     };

@@ -91,6 +91,7 @@ _SIGNATURES = {
     "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
+    "rlt_bilstm_rec_plan": (c_int, [c_int, c_int, c_int, P]),
     "rlt_to_position_major": (c_int, [P, c_int, c_int, c_int, P, P]),
     "rlt_from_position_major": (c_int, [P, c_int, c_int, c_int, P, P]),
     "rlt_choopy_embed": (c_int, [P, P, c_int, c_int, c_int, P, P]),
@@ -191,6 +192,24 @@ def attention_plan(S, B, H, HD, drop_p, have_images, precision=PRECISION_DEFAULT
         out[f] = tuple(n for i, n in enumerate(ATTN_PREPARE) if out[f] >> i & 1)
     out["images_kind"] = ATTN_IMAGES[out["images_kind"]]
     out["ws_kind"] = ATTN_WS[out["ws_kind"]]
+    return out
+
+
+LSTM_KERNELS = ("none", "f32", "x3", "x6", "x6w_single", "x6w_halves")            # RLT_LSTM_F32 .. RLT_LSTM_X6W_HALVES (0: unused)
+LSTM_PLAN_FIELDS = ("fwd", "bwd", "fwd_lists", "bwd_lists")
+
+
+class BilstmRecPlan(ctypes.Structure):
+    """struct rlt_bilstm_rec_plan: what the BiLSTM recurrence entry points decide for one call."""
+    _fields_ = [(f, c_int) for f in LSTM_PLAN_FIELDS]
+
+
+def bilstm_rec_plan(B, xin, precision=PRECISION_DEFAULT):
+    """-> dict of the plan's fields, the kernels as their names in LSTM_KERNELS."""
+    d = BilstmRecPlan()
+    check(load().rlt_bilstm_rec_plan(B, int(bool(xin)), precision, ctypes.byref(d)), "rlt_bilstm_rec_plan")
+    out = {f: int(getattr(d, f)) for f in LSTM_PLAN_FIELDS}
+    out["fwd"], out["bwd"] = LSTM_KERNELS[out["fwd"]], LSTM_KERNELS[out["bwd"]]
     return out
 
 
