@@ -759,6 +759,72 @@ int rlt_wass_loss_bwd(const float* p, const float* labels, const float* gscale, 
 int rlt_adam_step(float* p, const float* g, float* m, float* v, size_t n, int step,
                   float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ------------------------------------------------------------------ guarded optimizer step (csrc/optim.hip)
+ * torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam, with the gradient norm per step and per parameter tensor and a
+ * skip of steps whose gradient is not finite - decided on the device: no host read, no allocation, every launch ordered on
+ * `stream`, and no scalar argument that changes from step to step (the step count lives in the state).
+ *
+ * struct rlt_opt_state: 104 bytes of DEVICE memory owned by the caller, 8-byte aligned, zero-initialised by the caller before
+ * the first step and written only by the two entry points below (every member is 8 bytes wide up to `coef`: an int64 view of
+ * 13 words reads it).
+ *   step, skipped, clipped    steps applied / skipped as non-finite / applied with a coefficient below 1
+ *   nonfinite, nan_count      the last norm call: NaN and +-Inf elements of the bucket, and the NaN among them
+ *   sumsq, norm, max_abs      the last norm call: float64 sum of squares and max |g| over the FINITE elements; norm = sqrt of
+ *                             sumsq, or what torch's norm of such a gradient is when nonfinite > 0: NaN if nan_count > 0, else Inf
+ *   norm_sum, norm_max, norm_steps   running sum and maximum of `norm` over the norm calls whose gradient was finite, and their
+ *                             number (a trainer reads them once per epoch and zeroes them)
+ *   coef                      the last norm call's clip coefficient
+ *   apply, bc1, bc2_sqrt      scratch of the guarded step: its decision and the bias corrections of the step it applies
+ * struct rlt_grad_seg: one segment's figures - sumsq and max_abs over its finite elements, nonfinite its NaN / Inf count.
+ *
+ * The norm: one read of the flat fp32 gradient bucket g (n elements, n % 4 == 0, n <= 2^46, 16-byte aligned).  A segment is
+ * one slot of the bucket: seg_offsets (n_seg + 1) int64 in DEVICE memory, ascending multiples of 4 with seg_offsets[0] == 0 and
+ * seg_offsets[n_seg] == n; seg_out (n_seg) receives the segments' figures.  n_seg == 0 with seg_offsets NULL is one segment
+ * over the whole bucket (seg_out may then be NULL).  The bucket's figures are the fixed-order sum of the segments' and go to
+ * `state` with the norm and coef = min(1, max_norm / (norm + 1e-6)) - torch's rule, formed in float64 and rounded to float
+ * once; a NaN norm gives a NaN coefficient as in torch.  max_norm <= 0 or +Inf: no clipping, coef is exactly 1.0f.
+ * Every sum is float64 in an order fixed by n and the segment table alone (the bucket is cut into chunks of
+ * RLT_GRAD_NORM_CHUNK elements at absolute positions; csrc/optim.hip states the order): no float atomics, the same bits
+ * from every grid and every call.  The grid is min(chunks, RLT_GRAD_NORM_GRID) workgroups, one chunk per workgroup and trip;
+ * the two query functions return those two constants.  Three launches: the pass, the segments, the bucket.
+ * ws: the workspace query's bytes, 16-byte aligned (0 for n == 0, n % 4 != 0 or n_seg < 0).
+ * Errors before any launch: RLT_E_ARG (g, ws or state NULL, n == 0, n_seg < 0, max_norm NaN, n_seg > 0 without seg_offsets
+ * and seg_out, n_seg == 0 with seg_offsets; a segment table that is not as described above when the HOST can read it - pinned
+ * or managed memory, or a process without a device; a table in device memory cannot be read without a synchronising copy: it is
+ * the caller's duty, and the kernels stay inside g, ws and seg_out whatever it holds), RLT_E_SHAPE (n % 4, n > 2^46),
+ * RLT_E_ALIGN, RLT_E_WORKSPACE (ws off 16 bytes or too small).
+ * Algorithmic bytes: 4n read (+ 32 bytes written per chunk of 16 KB).
+ *
+ * The guarded step reads coef and nonfinite from `state` (so it follows a norm call on the same stream):
+ *   skip_nonfinite != 0 and nonfinite != 0: p, m, v stay byte for byte as they were, `step` too, skipped += 1;
+ *   otherwise t = ++step, clipped += 1 when coef < 1, and per element the arithmetic of rlt_adam_step at step t on
+ *   gr = g * coef + weight_decay * p - clipping acts on the raw gradient, the coupled L2 term is added after it, as
+ *   clip_grad_norm_ followed by torch.optim.Adam(weight_decay) does - with the bias corrections 1 - pow(beta, t) formed
+ *   in float64 on the device and rounded to float.  g is not modified.  Without skip_nonfinite a non-finite gradient or
+ *   coefficient propagates into p, m and v as it does in torch.
+ * p, g, m, v: n elements each, n % 4 == 0, 16-byte aligned (RLT_E_SHAPE / RLT_E_ALIGN).  Two launches: the decision (one lane)
+ * and the update.  Algorithmic bytes: 16n read, 12n written, as rlt_adam_step. */
+#define RLT_GRAD_NORM_CHUNK 4096
+#define RLT_GRAD_NORM_GRID  2048
+typedef struct rlt_opt_state {
+    int64_t step, skipped, clipped;
+    int64_t nonfinite, nan_count;
+    double sumsq, norm, max_abs;
+    double norm_sum, norm_max;
+    int64_t norm_steps;
+    float coef;
+    int32_t apply;
+    float bc1, bc2_sqrt;
+} rlt_opt_state;
+typedef struct rlt_grad_seg { double sumsq; int64_t nonfinite; double max_abs; } rlt_grad_seg;
+size_t rlt_grad_norm_chunk(void);
+int rlt_grad_norm_grid(void);
+size_t rlt_grad_norm_workspace(size_t n, int n_seg);
+int rlt_grad_norm(const float* g, size_t n, const int64_t* seg_offsets, int n_seg, float max_norm,
+                  void* ws, size_t ws_bytes, rlt_grad_seg* seg_out, rlt_opt_state* state, void* stream);
+int rlt_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, rlt_opt_state* state,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, int skip_nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,12 @@ _SIGNATURES = {
     "rlt_mmoe_mix_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rlt_mmoe_mix_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "rlt_adam_step": (c_int, [P, P, P, P, c_size_t, c_int, c_float, c_float, c_float, c_float, c_float, P]),
+    # guarded optimizer step: gradient norms, clipping, non-finite skip (csrc/optim.hip)
+    "rlt_grad_norm_chunk": (c_size_t, []),
+    "rlt_grad_norm_grid": (c_int, []),
+    "rlt_grad_norm_workspace": (c_size_t, [c_size_t, c_int]),
+    "rlt_grad_norm": (c_int, [P, c_size_t, P, c_int, c_float, P, c_size_t, P, P, P]),
+    "rlt_adam_step_guarded": (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
     # path-level entry points (one call per module forward / backward)
     "rlt_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "rlt_encoder_layer_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_size_t, P, c_size_t, c_int, P]),
@@ -211,6 +217,15 @@ def bilstm_rec_plan(B, xin, precision=PRECISION_DEFAULT):
     out = {f: int(getattr(d, f)) for f in LSTM_PLAN_FIELDS}
     out["fwd"], out["bwd"] = LSTM_KERNELS[out["fwd"]], LSTM_KERNELS[out["bwd"]]
     return out
+
+
+# rlt_opt_state as 13 int64 words (every member up to `coef` is 8 bytes wide); the float64 members through .view(torch.float64),
+# word 11 = (coef, apply) and word 12 = (bc1, bc2_sqrt) through .view(torch.float32)
+OPT_STATE_WORDS = 13
+OPT_STEP, OPT_SKIPPED, OPT_CLIPPED, OPT_NONFINITE, OPT_NAN = 0, 1, 2, 3, 4
+OPT_SUMSQ, OPT_NORM, OPT_MAX_ABS, OPT_NORM_SUM, OPT_NORM_MAX, OPT_NORM_STEPS = 5, 6, 7, 8, 9, 10
+OPT_COEF_F32 = 22                                  # index of `coef` in the float32 view
+GRAD_SEG_WORDS = 3                                 # rlt_grad_seg: sumsq (float64), nonfinite (int64), max_abs (float64)
 
 
 def encoder_ptrs(tensors):

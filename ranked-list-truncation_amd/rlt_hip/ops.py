@@ -1260,3 +1260,36 @@ def reward_matrix(labels, metric, tau=1.0, want_q=False, penalty=-1.0):
     q = _empty((B, S), labels) if want_q else None
     call("rlt_reward_matrix_ex", ptr(labels), ptr(coef), B, S, metric, float(penalty), tau, ptr(r), ptr(q), stream())
     return (r, q) if want_q else r
+
+
+# ------------------------------------------------------------------------------ optimizer
+def grad_norm(flat_grad, offsets=None, max_norm=None, state=None):
+    """rlt_grad_norm on a flat fp32 gradient bucket (numel % 4 == 0, on the GPU) in one read; no host synchronisation.
+    offsets: (n_seg + 1) int64 DEVICE tensor of ascending multiples of 4 from 0 to numel - FlatModel.offsets - for per-segment
+    figures, None for the bucket alone.  max_norm None / 0 / inf: no clipping (coef == 1).  state: an rlt_opt_state
+    (N.OPT_STATE_WORDS int64 zeros, device) to update, a fresh one otherwise.
+    Returns a dict of device tensors: norm, sumsq, max_abs (float64), coef (float32), nonfinite (int64), `state` itself, and
+    with offsets seg_sumsq, seg_max_abs (float64), seg_nonfinite (int64)."""
+    N.require_cuda(flat_grad, offsets)
+    if flat_grad.dtype != torch.float32 or flat_grad.dim() != 1 or not flat_grad.is_contiguous():
+        raise ValueError("grad_norm: a contiguous 1-D float32 bucket is required")
+    dev, n = flat_grad.device, flat_grad.numel()
+    n_seg = 0
+    if offsets is not None:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+            raise ValueError("grad_norm: offsets must be a contiguous int64 vector of n_seg + 1 entries")
+        n_seg = offsets.numel() - 1
+    if state is None:
+        state = torch.zeros(N.OPT_STATE_WORDS, dtype=torch.int64, device=dev)
+    seg = torch.zeros(max(n_seg, 1), N.GRAD_SEG_WORDS, dtype=torch.int64, device=dev)
+    ws_bytes = query("rlt_grad_norm_workspace", n, n_seg)
+    ws = N.byte_buffer(ws_bytes, dev)
+    call("rlt_grad_norm", ptr(flat_grad), n, ptr(offsets), n_seg, float(max_norm or 0.0), ptr(ws), ws_bytes, ptr(seg), ptr(state),
+         stream())
+    f64 = state.view(torch.float64)
+    out = {"norm": f64[N.OPT_NORM], "sumsq": f64[N.OPT_SUMSQ], "max_abs": f64[N.OPT_MAX_ABS],
+           "coef": state.view(torch.float32)[N.OPT_COEF_F32], "nonfinite": state[N.OPT_NONFINITE], "state": state}
+    if n_seg:
+        seg64 = seg.view(torch.float64)
+        out.update(seg_sumsq=seg64[:, 0], seg_nonfinite=seg[:, 1], seg_max_abs=seg64[:, 2])
+    return out

@@ -11,7 +11,8 @@ averaged over ranks, i.e. gradients are averaged with ONE all-reduce of the flat
 `FlatModel` re-points every parameter (and its .grad) of an nn.Module at views of two flat fp32
 buffers, so that zero_grad is one memset, the all-reduce is one collective on one buffer, and
 `FusedAdam` (torch.optim.Adam semantics: coupled L2, bias correction; run.py:104) is one
-`rlt_adam_step` launch.
+`rlt_adam_step` launch - or, with gradient-norm clipping, the non-finite skip or per-parameter norms switched on, one
+`rlt_grad_norm` pass over the gradient bucket followed by `rlt_adam_step_guarded`, all decided on the device.
 """
 import os
 
@@ -53,6 +54,11 @@ class FlatModel:
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
         self.numel = total
         self.params = params
+        # the slots as a segment table for the per-parameter gradient norms (rlt_grad_norm): n_slots + 1 ascending offsets, the last
+        # one = numel (a slot's padding up to 4 floats stays zero and belongs to it), and each slot's name for reporting
+        self.offsets = torch.tensor(offs + [total], dtype=torch.int64, device=dev)
+        by_id = {id(p): n for n, p in model.named_parameters()}
+        self.names = [by_id[id(p)] for p in params]
         with torch.no_grad():
             for p, o in zip(params, offs):
                 n = p.numel()
@@ -89,14 +95,33 @@ class FlatModel:
 
 
 class FusedAdam:
-    """torch.optim.Adam(lr, betas, eps, weight_decay) on a FlatModel, one HIP launch per step."""
+    """torch.optim.Adam(lr, betas, eps, weight_decay) on a FlatModel, one HIP launch per step.
 
-    def __init__(self, flat: FlatModel, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    max_grad_norm / skip_nonfinite / segment_norms (all off by default: step() is then the one rlt_adam_step launch) switch to
+    the guarded step: rlt_grad_norm over flat_grad - the bucket's norm, the clip coefficient of torch's clip_grad_norm_, the
+    non-finite count and, with segment_norms, the figures of every parameter tensor - followed by rlt_adam_step_guarded, which
+    applies the coefficient inside the update (flat_grad itself is left unclipped) and, with skip_nonfinite, leaves the
+    parameters and both moments untouched when the gradient holds a NaN or an Inf.  The step count then lives on the device;
+    nothing is allocated per step and the host reads nothing until epoch_stats() / state_dict()."""
+
+    def __init__(self, flat: FlatModel, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None, skip_nonfinite=False, segment_norms=False):
         self.flat = flat
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.flat_param)
         self.exp_avg_sq = torch.zeros_like(flat.flat_param)
         self.steps = 0
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
+        self.skip_nonfinite, self.segment_norms = bool(skip_nonfinite), bool(segment_norms)
+        self.guarded = self.max_grad_norm > 0.0 or self.skip_nonfinite or self.segment_norms
+        if self.guarded:
+            dev = flat.flat_param.device
+            self.n_seg = len(flat.params) if self.segment_norms else 0
+            self.opt_state = torch.zeros(N.OPT_STATE_WORDS, dtype=torch.int64, device=dev)
+            self.seg_stats = torch.zeros(max(self.n_seg, 1), N.GRAD_SEG_WORDS, dtype=torch.int64, device=dev)
+            self.ws_bytes = N.query("rlt_grad_norm_workspace", flat.numel, self.n_seg)
+            self.ws = N.byte_buffer(self.ws_bytes, dev)
+            self.totals = {"clipped": 0, "skipped": 0}          # of the epochs that epoch_stats(reset=True) has closed
 
     def zero_grad(self):
         self.flat.zero_grad()
@@ -105,12 +130,65 @@ class FusedAdam:
         f = self.flat
         if not f.flat_param.is_cuda:
             raise RuntimeError("FusedAdam runs on the GPU (rlt_adam_step); no CPU fallback exists")
+        if self.guarded:
+            N.call("rlt_grad_norm", N.ptr(f.flat_grad), f.numel, N.ptr(f.offsets) if self.n_seg else None, self.n_seg,
+                   self.max_grad_norm, N.ptr(self.ws), self.ws_bytes, N.ptr(self.seg_stats), N.ptr(self.opt_state), N.stream())
+            N.call("rlt_adam_step_guarded", N.ptr(f.flat_param), N.ptr(f.flat_grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+                   f.numel, N.ptr(self.opt_state), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                   int(self.skip_nonfinite), N.stream())
+            return
         self.steps += 1
         N.call("rlt_adam_step", N.ptr(f.flat_param), N.ptr(f.flat_grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
                f.numel, self.steps, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, N.stream())
 
+    def _need_guard(self):
+        if not self.guarded:
+            raise RuntimeError("gradient statistics exist only with max_grad_norm, skip_nonfinite or segment_norms set")
+
+    def grad_stats(self):
+        """The last step's figures as DEVICE tensors (views of the optimizer state: no copy, no synchronisation): norm, sumsq
+        and max_abs float64, coef float32, nonfinite int64; with segment_norms also seg_sumsq, seg_max_abs (float64) and
+        seg_nonfinite (int64), one entry per parameter tensor in the order of FlatModel.names."""
+        self._need_guard()
+        st, f64 = self.opt_state, self.opt_state.view(torch.float64)
+        out = {"norm": f64[N.OPT_NORM], "sumsq": f64[N.OPT_SUMSQ], "max_abs": f64[N.OPT_MAX_ABS],
+               "coef": st.view(torch.float32)[N.OPT_COEF_F32], "nonfinite": st[N.OPT_NONFINITE]}
+        if self.segment_norms:
+            seg64 = self.seg_stats.view(torch.float64)
+            out.update(seg_sumsq=seg64[:, 0], seg_nonfinite=self.seg_stats[:, 1], seg_max_abs=seg64[:, 2])
+        return out
+
+    def epoch_stats(self, reset=True):
+        """The one host read: mean and maximum gradient norm over the steps since the last reset whose gradient was finite
+        (NaN / 0.0 when there was none), the number of those steps, the clipped and skipped steps since the last reset and, with
+        segment_norms, the last step's norm of every parameter tensor by name.  reset=True zeroes the running figures and the
+        two counters on the device; state_dict() keeps their totals."""
+        self._need_guard()
+        words = self.opt_state.clone()
+        seg = self.seg_stats.clone() if self.segment_norms else None
+        if reset:
+            self.opt_state[N.OPT_NORM_SUM:N.OPT_NORM_STEPS + 1].zero_()
+            self.opt_state[N.OPT_SKIPPED:N.OPT_CLIPPED + 1].zero_()
+        words = words.cpu()                                     # the synchronisation
+        f64 = words.view(torch.float64)
+        n = int(words[N.OPT_NORM_STEPS])
+        out = {"grad_norm_mean": float(f64[N.OPT_NORM_SUM]) / n if n else float("nan"), "grad_norm_max": float(f64[N.OPT_NORM_MAX]),
+               "finite_steps": n, "clipped_steps": int(words[N.OPT_CLIPPED]), "skipped_steps": int(words[N.OPT_SKIPPED])}
+        if reset:
+            self.totals["clipped"] += out["clipped_steps"]
+            self.totals["skipped"] += out["skipped_steps"]
+        if seg is not None:
+            norms = seg.view(torch.float64)[:, 0].sqrt().cpu().tolist()
+            out["segment_norms"] = dict(zip(self.flat.names, norms))
+        return out
+
     def state_dict(self):
-        return {"steps": self.steps, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        if not self.guarded:
+            return {"steps": self.steps, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        words = self.opt_state.cpu()                            # the applied step count lives on the device
+        return {"steps": int(words[N.OPT_STEP]), "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+                "clipped_steps": self.totals["clipped"] + int(words[N.OPT_CLIPPED]),
+                "skipped_steps": self.totals["skipped"] + int(words[N.OPT_SKIPPED])}
 
 
 def shard_batch(x, y, rank, world):

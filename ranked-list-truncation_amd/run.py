@@ -172,7 +172,7 @@ class Trainer:
             self.load_model()
         self.flat = FlatModel(self.model)
         self.flat.broadcast_params()
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay)   # run.py:104
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **grad_guard_kwargs(args))   # run.py:104
         ops.set_seed_stream(self.rank)          # same torch seed on every rank, different dropout masks
         self.writer = ScalarLog(getattr(args, "tensorboard_dir", None) if self.rank == 0 else None)   # run.py:111
         self.history = []                       # per epoch: train / test (loss, f1, dcg) means
@@ -222,6 +222,9 @@ class Trainer:
         self.writer.add_scalar('train/F1_epoch', f1, epoch)
         self.writer.add_scalar('train/DCG_epoch', dcg, epoch)
         self.history.append({"epoch": epoch, "train": (loss, f1, dcg)})
+        grad = log_grad_guard(self.writer, self.optimizer, epoch)
+        if grad is not None:
+            self.history[-1]["grad"] = grad
         if self.rank == 0:
             logging.info('\nEpoch: {} | Epoch Time: {:.2f} s'.format(epoch, time.time() - start))
             logging.info('\tTrain: loss = {} | f1 = {:.6f} | dcg = {:.6f}\n'.format(loss, f1, dcg))
@@ -400,6 +403,40 @@ class Trainer:
         return self.best_test_f1, self.best_test_dcg
 
 
+GRAD_GUARD_TAGS = ('train/grad_norm_epoch', 'train/grad_norm_max_epoch', 'train/clipped_steps', 'train/skipped_steps')
+
+
+def add_grad_guard_arguments(p):
+    """--clip-grad-norm / --skip-nonfinite of run.py, verify_probe.py and verify_BMT.py: FusedAdam's guarded step."""
+    p.add_argument('--clip-grad-norm', type=float, default=0.0,
+                   help="F > 0: clip the gradient's global L2 norm to F before every Adam step (torch's clip_grad_norm_ rule, on the "
+                        "device, after the gradient all-reduce) and log train/grad_norm_epoch, train/grad_norm_max_epoch, "
+                        "train/clipped_steps, train/skipped_steps per epoch; 0: off")
+    p.add_argument('--skip-nonfinite', type=int, default=0, choices=(0, 1),
+                   help="1: a step whose gradient holds a NaN or an Inf leaves parameters and Adam moments untouched and is counted "
+                        "in train/skipped_steps")
+
+
+def grad_guard_kwargs(args):
+    """FusedAdam's keyword arguments for the two flags; empty with both at their defaults (the plain rlt_adam_step path).  The norm
+    is taken inside step(), i.e. after FlatModel.all_reduce_grads(): every rank forms the same coefficient from the same bucket."""
+    clip, skip = float(getattr(args, "clip_grad_norm", 0) or 0), bool(getattr(args, "skip_nonfinite", 0))   # (drivers build their own Namespace)
+    return dict(max_grad_norm=clip if clip > 0 else None, skip_nonfinite=skip) if clip > 0 or skip else {}
+
+
+def log_grad_guard(writer, optimizer, epoch):
+    """The epoch's one read of the optimizer state, under GRAD_GUARD_TAGS; returns the same values for --history-json (None, and
+    nothing logged, when the guarded step is off)."""
+    if not optimizer.guarded:
+        return None
+    gs = optimizer.epoch_stats(reset=True)
+    vals = (gs["grad_norm_mean"], gs["grad_norm_max"], gs["clipped_steps"], gs["skipped_steps"])
+    for tag, v in zip(GRAD_GUARD_TAGS, vals):
+        writer.add_scalar(tag, v, epoch)
+    # an epoch without one finite gradient has no mean norm (JSON has no NaN)
+    return {tag.split('/', 1)[1]: (v if math.isfinite(v) else None) for tag, v in zip(GRAD_GUARD_TAGS, vals)}
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Truncation Model Trainer Args (HIP hot path)")
     p.add_argument('--retrieve-data', type=str, default='robust04')
@@ -449,6 +486,7 @@ def build_parser():
                         "(dense columns) + (dictionary size); without it bicut reads the three attncut columns as before")
     p.add_argument('--bicut-vocab', type=int, default=None,
                    help="dictionary size V of --bicut-stats (the reference: 231448); default 1 + the largest term id of the file")
+    add_grad_guard_arguments(p)
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Truncation'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

@@ -75,7 +75,7 @@ class Trainer:
         E = width if self.ft else feat
         self.model = (TaskC if self.verify_type == 'c' else TaskR)(d_model=E).to(self.device)
         self.flat = FlatModel(self.model)
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay)
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
         self.writer = run.ScalarLog(args.tensorboard_dir)
 
     def features(self, X):
@@ -123,6 +123,9 @@ class Trainer:
         self.writer.add_scalar('train/loss_epoch', loss, epoch)
         self.writer.add_scalar('train/{}_epoch'.format(self.metric_name), metric, epoch)
         self.history.append({"epoch": epoch, "train": (loss, metric)})
+        grad = run.log_grad_guard(self.writer, self.optimizer, epoch)
+        if grad is not None:
+            self.history[-1]["grad"] = grad
         logging.info('\nEpoch: {} | Epoch Time: {:.2f} s'.format(epoch, time.time() - start))
         logging.info('\tTrain: loss = {} | {} = {:.6f}\n'.format(loss, self.metric_name, metric))
 
@@ -168,6 +171,7 @@ def build_parser():
     p.add_argument('--synthetic', type=int, default=0, help="write a robust04-shaped synthetic set into --dataset-base first")
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--history-json', type=str, default=None, help="per-epoch train / test means and the train metric list")
+    run.add_grad_guard_arguments(p)
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Verify'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

@@ -67,7 +67,7 @@ def base_trainer(args, model, loaders, device):
     t.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
     t.multi_task = True
     t.flat = FlatModel(model)
-    t.optimizer = FusedAdam(t.flat, lr=args.lr, weight_decay=args.weight_decay)
+    t.optimizer = FusedAdam(t.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
     t.writer = run.ScalarLog(os.path.join(args.tensorboard_dir, 'base') if args.tensorboard_dir else None)
     return t
 
@@ -91,7 +91,7 @@ class Trainer:
                                         dropout=args.dropout, num_experts=2).to(self.device)
         self.probe = Probe().to(self.device)
         self.flat = FlatModel(self.probe)
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay)
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
         self.writer = run.ScalarLog(args.tensorboard_dir)
         self.base_history, self.history = None, []
         self.step = 0
@@ -123,6 +123,9 @@ class Trainer:
             n += 1
         means = {name: tot[name] / n for name in TAGS}
         self.history.append({"epoch": epoch, **means})
+        grad = run.log_grad_guard(self.writer, self.optimizer, epoch)
+        if grad is not None:
+            self.history[-1]["grad"] = grad
         logging.info('\tProbe epoch {}: '.format(epoch) + ' | '.join('{} = {:.6f}'.format(k, v) for k, v in means.items()))
 
     def run(self):
@@ -172,6 +175,7 @@ def build_parser():
     p.add_argument('--synthetic', type=int, default=0, help="write a robust04-shaped synthetic set into --dataset-base first")
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--history-json', type=str, default=None, help="the base's per-epoch history and the probes' epoch means")
+    run.add_grad_guard_arguments(p)
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Probe'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

@@ -717,6 +717,67 @@ def bicut_sparse(B=20, S=300, V=231448, n_docs=60000, draws=200, rounds=15):
           f"{float(np.median(ts)):10.1f} us (min {min(ts):.1f}, max {max(ts):.1f})", flush=True)
 
 
+def optim(reps=15):
+    """The optimizer step at AttnCut's 1,846,785 parameters (rounded up to its 4-float slots) and at BiCut's 237.6 M: (a)
+    rlt_adam_step alone, (b) rlt_grad_norm + rlt_adam_step_guarded (and each of the two on its own), (c) the torch composition
+    the guarded step replaces - vector_norm of the float64-cast bucket, isfinite().all(), mul_ by the clamped coefficient, then
+    rlt_adam_step - with no host read either.  HIP events around single alternating launches, the median of `reps`; GB/s on each
+    pass's algorithmic bytes (Adam 28 n: p, g, m, v read, p, m, v written; the norm 4 n)."""
+    lr, b1, b2, eps, wd, max_norm = 3e-5, 0.9, 0.999, 1e-8, 0.005, 1e9
+    for label, n in (("AttnCut", (1846785 + 3) // 4 * 4), ("BiCut", 237600000)):
+        gen = torch.Generator(device=dev).manual_seed(3)
+        p, g = torch.randn(n, device=dev, generator=gen), torch.randn(n, device=dev, generator=gen) * 1e-3
+        m, v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        state = torch.zeros(N.OPT_STATE_WORDS, dtype=torch.int64, device=dev)
+        wsb = N.query("rlt_grad_norm_workspace", n, 0)
+        ws = N.byte_buffer(wsb, dev)
+        t = [0]
+
+        def adam():
+            t[0] += 1
+            call("rlt_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), n, t[0], lr, b1, b2, eps, wd, stream())
+
+        def norm():
+            call("rlt_grad_norm", ptr(g), n, None, 0, max_norm, ptr(ws), wsb, None, ptr(state), stream())
+
+        def guarded():
+            call("rlt_adam_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(state), lr, b1, b2, eps, wd, 1, stream())
+
+        def both():
+            norm()
+            guarded()
+
+        def composed():
+            nrm = torch.linalg.vector_norm(g.double())
+            torch.isfinite(g).all()
+            g.mul_((max_norm / (nrm + 1e-6)).clamp(max=1.0).float())
+            adam()
+        fns = (("adam_step", adam, 28), ("grad_norm", norm, 4), ("adam_step_guarded", guarded, 28), ("norm+guarded", both, 32),
+               ("torch composition", composed, 32))
+        times = {name: [] for name, _, _ in fns}
+        for _, fn, _ in fns:
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for name, fn, _ in fns:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(b))
+        med = {name: sorted(ts)[reps // 2] for name, ts in times.items()}
+        for name, _, per in fns:
+            ms = med[name]
+            print(f"optim {label:8s} n={n:10d} {name:18s}: {ms * 1e3:9.1f} us  {per * n / ms / 1e6:8.1f} GB/s on {per} n bytes", flush=True)
+        print(f"optim {label:8s} norm+guarded / adam_step: {med['norm+guarded'] / med['adam_step']:.2f}x;  torch composition / norm+guarded: "
+              f"{med['torch composition'] / med['norm+guarded']:.2f}x"
+              + ("  (the guarded step is SLOWER than the torch composition here)" if med['norm+guarded'] > med['torch composition'] else ""),
+              flush=True)
+        del p, g, m, v
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
