@@ -825,6 +825,66 @@ int rlt_grad_norm(const float* g, size_t n, const int64_t* seg_offsets, int n_se
 int rlt_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, rlt_opt_state* state,
                           float lr, float beta1, float beta2, float eps, float weight_decay, int skip_nonfinite, void* stream);
 
+/* ------------------------------------------------------------------ paired significance tests (csrc/compare.hip)
+ * Is system m better than the baseline on the same queries?  base (Q) and sys (M rows of Q, leading dimension ld >= Q) are float32
+ * per-query values in one query order (columns of run.py --report-out).  One call leaves, per system, a record of
+ * RLT_CMP_WORDS 8-byte words (int64 unless marked f64) and, optionally, the R replicate statistics of two resampling tests.
+ * d[m][q] = (double)sys[m][q] - (double)base[q], exact in float64.  A pair with a NaN or Inf member is counted in NONFINITE, enters
+ * the resampling with d = 0 and stays out of N, the sums and the win / tie / loss counts.
+ *   RLT_CMP_N          finite pairs                       RLT_CMP_WINS / _TIES / _LOSSES   d > 0, d == 0, d < 0
+ *   RLT_CMP_SUM_BASE   f64, sum of base                   RLT_CMP_NONFINITE                pairs with a NaN / Inf member
+ *   RLT_CMP_SUM_SYS    f64, sum of sys                    RLT_CMP_T_OBS                    f64, the observed statistic: sum of d
+ *   RLT_CMP_SUM_D      f64, sum of d                      RLT_CMP_RAND_GE                  replicates with |T_r| >= |T_obs|
+ *   RLT_CMP_SSD        f64, sum of (d - mean)^2, a        RLT_CMP_BOOT_LE0 / _BOOT_GE0     bootstrap sums <= 0 / >= 0
+ *                      second pass about SUM_D / N        RLT_CMP_RESAMPLES, RLT_CMP_FORM  R and the plan's form; RESERVED: 0
+ * Randomization (Fisher sign flip): T_r = sum_q s(r,q) d[m][q], s = -1 where bit (q & 31) of word(r, q >> 5) is set, else +1.
+ * Paired bootstrap: B_r = sum_{j<Q} d[m][idx(r,j)], idx(r,j) = (u(r,j) * Q) >> 32 on the 64-bit product.  All M systems see the
+ * same signs and the same indices.  With mix32 and row_hash the two 32-bit functions of csrc/common.h (arithmetic mod 2^32):
+ *   draw(seed, r, c) = mix32(row_hash(seed, r) ^ mix32(c + 0x7F4A7C15))
+ *   word(r, k) = draw(seed, r, k)         u(r, j) = draw(mix32(seed ^ 0xA511E9B3), r, j)
+ * a pure function of (seed, r, c).  idx is floor(u Q / 2^32): each index has probability within 2^-32 of 1/Q, a relative bias of
+ * at most Q / 2^32.  T_obs is formed by the replicate code with every sign plus, in the same order: a replicate that draws all
+ * plus or all minus ties with it bit for bit.  Every sum is float64 in an order fixed by Q, M and R (csrc/compare.hip states
+ * it); no float atomics; two calls give the same bits.
+ * rand_stat, boot_stat: (M, R) float64, row m = T_r / B_r of system m; either may be NULL.
+ * Limits: 1 <= Q <= 2^26, 1 <= M <= RLT_COMPARE_MAX_SYSTEMS, 0 <= R <= 2^20.
+ * The plan: RLT_COMPARE_RESIDENT while Q <= resident_max_q = 160 KB / (8 M) - d sits in LDS (lds_bytes), a workgroup of 16
+ * wavefronts walks 16 * replicates_per_wave replicates, a wavefront per replicate; RLT_COMPARE_CHUNKED beyond - the grid runs over
+ * replicates x `chunks` chunks of `chunk` = RLT_COMPARE_CHUNK queries, partial sums [chunk][m][r] go to the workspace and are added
+ * in ascending chunk order; the bootstrap gathers then go through L2 / global memory.  `chunk` and resident_max_q are filled in
+ * both forms.  The workspace holds d (8 Q M bytes), the partials (16 chunks M (R + 1) bytes), the sums and the moment records.
+ * The plan and the workspace query answer without a GPU (0 bytes for dimensions outside the limits).  Seven launches, no
+ * allocation, no host synchronisation.
+ * Errors before any launch: RLT_E_ARG (base, sys, ws, record or the plan's out NULL; Q < 1, M < 1, R < 0; ld < Q), RLT_E_SHAPE (Q,
+ * M or R above its limit), RLT_E_ALIGN (base / sys off 4 bytes, record / rand_stat / boot_stat off 8), RLT_E_WORKSPACE (ws off 16
+ * bytes or too small). */
+#define RLT_COMPARE_RESIDENT 1
+#define RLT_COMPARE_CHUNKED  2
+#define RLT_COMPARE_CHUNK    32768
+#define RLT_COMPARE_MAX_SYSTEMS 8
+#define RLT_CMP_N 0
+#define RLT_CMP_SUM_BASE 1
+#define RLT_CMP_SUM_SYS 2
+#define RLT_CMP_SUM_D 3
+#define RLT_CMP_SSD 4
+#define RLT_CMP_WINS 5
+#define RLT_CMP_TIES 6
+#define RLT_CMP_LOSSES 7
+#define RLT_CMP_NONFINITE 8
+#define RLT_CMP_T_OBS 9
+#define RLT_CMP_RAND_GE 10
+#define RLT_CMP_BOOT_LE0 11
+#define RLT_CMP_BOOT_GE0 12
+#define RLT_CMP_RESAMPLES 13
+#define RLT_CMP_FORM 14
+#define RLT_CMP_RESERVED 15
+#define RLT_CMP_WORDS 16
+struct rlt_paired_compare_plan { int form, chunk, resident_max_q, chunks, replicates_per_wave, lds_bytes; };
+int rlt_paired_compare_plan(int Q, int M, int R, struct rlt_paired_compare_plan* out);
+size_t rlt_paired_compare_workspace(int Q, int M, int R);
+int rlt_paired_compare(const float* base, const float* sys, int ld, int Q, int M, int R, uint32_t seed, void* ws, size_t ws_bytes,
+                       int64_t* record, double* rand_stat, double* boot_stat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

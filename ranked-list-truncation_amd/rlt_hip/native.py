@@ -110,6 +110,10 @@ _SIGNATURES = {
     "rlt_grad_norm_workspace": (c_size_t, [c_size_t, c_int]),
     "rlt_grad_norm": (c_int, [P, c_size_t, P, c_int, c_float, P, c_size_t, P, P, P]),
     "rlt_adam_step_guarded": (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    # paired significance tests between per-query columns (csrc/compare.hip)
+    "rlt_paired_compare_plan": (c_int, [c_int, c_int, c_int, P]),
+    "rlt_paired_compare_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "rlt_paired_compare": (c_int, [P, P, c_int, c_int, c_int, c_int, c_uint32, P, c_size_t, P, P, P, P]),
     # path-level entry points (one call per module forward / backward)
     "rlt_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "rlt_encoder_layer_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_size_t, P, c_size_t, c_int, P]),
@@ -226,6 +230,30 @@ OPT_STEP, OPT_SKIPPED, OPT_CLIPPED, OPT_NONFINITE, OPT_NAN = 0, 1, 2, 3, 4
 OPT_SUMSQ, OPT_NORM, OPT_MAX_ABS, OPT_NORM_SUM, OPT_NORM_MAX, OPT_NORM_STEPS = 5, 6, 7, 8, 9, 10
 OPT_COEF_F32 = 22                                  # index of `coef` in the float32 view
 GRAD_SEG_WORDS = 3                                 # rlt_grad_seg: sumsq (float64), nonfinite (int64), max_abs (float64)
+
+
+# the record of rlt_paired_compare: CMP_WORDS 8-byte words per system (RLT_CMP_*), the float64 ones through .view(torch.float64)
+CMP_WORDS = 16
+(CMP_N, CMP_SUM_BASE, CMP_SUM_SYS, CMP_SUM_D, CMP_SSD, CMP_WINS, CMP_TIES, CMP_LOSSES, CMP_NONFINITE, CMP_T_OBS, CMP_RAND_GE,
+ CMP_BOOT_LE0, CMP_BOOT_GE0, CMP_RESAMPLES, CMP_FORM, CMP_RESERVED) = range(16)
+CMP_F64_WORDS = (CMP_SUM_BASE, CMP_SUM_SYS, CMP_SUM_D, CMP_SSD, CMP_T_OBS)
+CMP_FORMS = ("none", "resident", "chunked")                                         # RLT_COMPARE_RESIDENT, RLT_COMPARE_CHUNKED
+CMP_MAX_Q, CMP_MAX_SYSTEMS, CMP_MAX_R = 1 << 26, 8, 1 << 20
+CMP_PLAN_FIELDS = ("form", "chunk", "resident_max_q", "chunks", "replicates_per_wave", "lds_bytes")
+
+
+class PairedComparePlan(ctypes.Structure):
+    """struct rlt_paired_compare_plan: what rlt_paired_compare decides for one call."""
+    _fields_ = [(f, c_int) for f in CMP_PLAN_FIELDS]
+
+
+def paired_compare_plan(Q, M, R):
+    """-> dict of the plan's fields, the form as its name in CMP_FORMS."""
+    d = PairedComparePlan()
+    check(load().rlt_paired_compare_plan(Q, M, R, ctypes.byref(d)), "rlt_paired_compare_plan")
+    out = {f: int(getattr(d, f)) for f in CMP_PLAN_FIELDS}
+    out["form"] = CMP_FORMS[out["form"]]
+    return out
 
 
 def encoder_ptrs(tensors):

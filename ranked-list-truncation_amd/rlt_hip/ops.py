@@ -1293,3 +1293,30 @@ def grad_norm(flat_grad, offsets=None, max_norm=None, state=None):
         seg64 = seg.view(torch.float64)
         out.update(seg_sumsq=seg64[:, 0], seg_nonfinite=seg[:, 1], seg_max_abs=seg64[:, 2])
     return out
+
+
+def paired_compare(base, systems, resamples, seed, keep_stats=True):
+    """rlt_paired_compare: the paired randomization test and the paired bootstrap of M systems against a baseline on the same
+    Q queries.  base (Q,), systems (M, Q) or (Q,) float32 on the GPU, in one query order; `resamples` replicates of each test from
+    the 32-bit `seed`.  Returns a dict of device tensors - record (M, N.CMP_WORDS) int64 (the float64 words through
+    .view(torch.float64)), and with keep_stats rand_stat and boot_stat (M, resamples) float64, else None.  No host synchronisation."""
+    N.require_cuda(base, systems)
+    if systems.dim() == 1:
+        systems = systems.unsqueeze(0)
+    if base.dim() != 1 or systems.dim() != 2 or systems.shape[1] != base.numel():
+        raise ValueError(f"paired_compare: base (Q,) and systems (M, Q) expected; got {tuple(base.shape)} and {tuple(systems.shape)}")
+    base, systems = N.f32c(base.detach()), N.f32c(systems.detach())
+    M, Q = systems.shape
+    R = int(resamples)
+    dev = base.device
+    record = torch.empty((M, N.CMP_WORDS), dtype=torch.int64, device=dev)
+    rand_stat = torch.empty((M, R), dtype=torch.float64, device=dev) if keep_stats else None
+    boot_stat = torch.empty((M, R), dtype=torch.float64, device=dev) if keep_stats else None
+    ws_bytes = query("rlt_paired_compare_workspace", Q, M, R)
+    if ws_bytes == 0:
+        raise ValueError(f"paired_compare: 1 <= Q <= {N.CMP_MAX_Q}, 1 <= M <= {N.CMP_MAX_SYSTEMS}, 0 <= resamples <= {N.CMP_MAX_R}; "
+                         f"got Q = {Q}, M = {M}, resamples = {R}")
+    ws = N.byte_buffer(ws_bytes, dev)
+    call("rlt_paired_compare", ptr(base), ptr(systems), Q, Q, M, R, int(seed) & 0xFFFFFFFF, ptr(ws), ws_bytes, ptr(record),
+         ptr(rand_stat) if keep_stats and R else None, ptr(boot_stat) if keep_stats and R else None, stream())
+    return {"record": record, "rand_stat": rand_stat, "boot_stat": boot_stat}

@@ -363,6 +363,20 @@ class Trainer:
                  summary=np.asarray(json.dumps(summaries)), **{k: np.concatenate(v) for k, v in arrays.items()}, **per_len)
         return summaries
 
+    def compare(self, path, others):
+        """--compare-to A.npz[,B.npz]: the report just written at `path` against the named ones (each of them the baseline of one
+        comparison), on the run's criterion: one logged line per file."""
+        from utils.compare import compare_reports
+        fresh = path if path.endswith(".npz") else path + ".npz"
+        lines = []
+        for other in [o for o in others.split(",") if o]:
+            cmp = compare_reports([other, fresh], metric=self.args.criterion, baseline=0,
+                                  resamples=10000, seed=self.args.seed or 0, device=self.device)
+            lines += cmp.lines()
+        for line in lines:
+            logging.info('\tCompare: {}'.format(line))
+        return lines
+
     def draw(self, epoch):
         """--draw 1 (run.py:188): for every test batch of more than 40 lists, the two curves `Trainer.plot` draws (run.py:262-283,
         tau = 0.9) into the scalar log.  The batches are the test buckets in file order."""
@@ -392,6 +406,8 @@ class Trainer:
         if getattr(self.args, "report_out", None) and self.rank == 0:
             self.report_results = self.report(self.args.report_out, getattr(self.args, "report_split", "test"),
                                               bool(getattr(self.args, "report_labels", 1)))
+            if getattr(self.args, "compare_to", None):
+                self.compare_lines = self.compare(self.args.report_out, self.args.compare_to)
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -475,6 +491,9 @@ def build_parser():
                    help="rank 0 writes a per-query cut report of the final model (.npz: k, winning value, margin, F1 / DCG at the cut, "
                         "each list's best and the count of better cuts, keyed by query id; per list length the k histogram, the "
                         "reward / prediction curves and the summary); with --epochs 0 --ft 1 --model-path CKPT it reports a checkpoint")
+    p.add_argument('--compare-to', type=str, default=None,
+                   help="A.npz[,B.npz]: after --report-out, rank 0 compares the fresh report with each named one query by query "
+                        "(paired randomization test, bootstrap interval, sign and t statistics) and logs one line per file")
     p.add_argument('--report-split', type=str, default='test', choices=('train', 'test'))
     p.add_argument('--report-labels', type=int, default=1, choices=(0, 1), help="0: label-free report (k, winning value, margin only)")
     p.add_argument('--draw', type=int, default=0, choices=(0, 1),

@@ -778,6 +778,142 @@ def optim(reps=15):
         torch.cuda.empty_cache()
 
 
+def compare():
+    """The paired comparison pass (rlt_paired_compare: R sign-flip replicates and R bootstrap replicates of M systems over Q
+    queries) against the best torch composition of the same two statistics, tiled over replicates so that its tensors fit.
+    The composition is searched, each half on its own: the randomization sums over {int8 randint bits, bits unpacked from int32
+    random words} x {signs @ d, 2 (bits @ d) - sum d, d @ signs.T, where(bit, -d, d).sum per system}; the bootstrap sums over
+    d[:, idx].sum with int64 and int32 indices, dT[idx].sum and dT.index_select(int32).sum.  Every form is timed at tiles that
+    grow by 4 until its per-replicate time stops falling (or the tile's tensors pass TILE_BYTES, or a gather 2^31 elements), on up to two tiles' worth
+    after a warm-up tile; the fastest (form, tile) of each half makes the composition that is timed over all R.  HIP events
+    around single alternating calls, the median of `reps` (15 at the small shape, 7 at the large ones, where a composition
+    pass takes seconds), with the minimum and maximum; draws = 2 R Q (one sign and one index per replicate and query)."""
+    TILE_BYTES = 96e9
+    shifts = torch.arange(32, dtype=torch.int32, device=dev)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    for Q, M, R, first_tile, reps in ((1 << 20, 1, 10000, 64, 7), (1 << 20, 4, 10000, 64, 7), (250, 4, 100000, 1024, 15)):
+        gen = torch.Generator(device=dev).manual_seed(5)
+        base = torch.rand(Q, device=dev, generator=gen)
+        sys_ = base[None, :] + 0.05 * torch.randn(M, Q, device=dev, generator=gen)
+        plan = N.paired_compare_plan(Q, M, R)
+        wsb = N.query("rlt_paired_compare_workspace", Q, M, R)
+        ws = N.byte_buffer(wsb, dev)
+        rec = torch.zeros(M, N.CMP_WORDS, dtype=torch.int64, device=dev)
+        rs, bs = torch.empty(M, R, dtype=torch.float64, device=dev), torch.empty(M, R, dtype=torch.float64, device=dev)
+        d = sys_.double() - base.double()[None, :]
+        dT = d.t().contiguous()
+        t_obs = d.sum(1)
+
+        def kernel():
+            call("rlt_paired_compare", ptr(base), ptr(sys_), Q, Q, M, R, 7, ptr(ws), wsb, ptr(rec), ptr(rs), ptr(bs), stream())
+
+        def bits_int8(t):
+            return torch.randint(0, 2, (t, Q), device=dev, dtype=torch.int8)
+
+        def bits_words(t):
+            w = torch.randint(-2 ** 31, 2 ** 31, (t, (Q + 31) // 32), device=dev, dtype=torch.int32)
+            return ((w[:, :, None] >> shifts) & 1).reshape(t, -1)[:, :Q]
+
+        def s_matmul(b):
+            return (b.double() * 2 - 1) @ dT                                    # (t, M)
+
+        def s_matmul01(b):
+            return 2 * (b.double() @ dT) - t_obs[None, :]
+
+        def s_dmatmul(b):
+            return (d @ (b.double() * 2 - 1).t()).t()
+
+        def s_where(b):
+            nz = b.bool()
+            return torch.stack([torch.where(nz, -d[m], d[m]).sum(1) for m in range(M)], 1)
+
+        def g_adv64(t):
+            return d[:, torch.randint(0, Q, (t, Q), device=dev)].sum(-1)        # (M, t)
+
+        def g_adv32(t):
+            return d[:, torch.randint(0, Q, (t, Q), device=dev, dtype=torch.int32)].sum(-1)
+
+        def g_rows64(t):
+            return dT[torch.randint(0, Q, (t, Q), device=dev)].sum(1).t()
+
+        def g_select32(t):
+            idx = torch.randint(0, Q, (t * Q,), device=dev, dtype=torch.int32)
+            return dT.index_select(0, idx).view(t, Q, M).sum(1).t()
+
+        sign_forms = {f"{bn}+{sn}": (lambda t, bf=bf, sf=sf: sf(bf(t)))
+                      for bn, bf in (("int8", bits_int8), ("words", bits_words))
+                      for sn, sf in (("signs@d", s_matmul), ("2(bits@d)-sum", s_matmul01), ("d@signs.T", s_dmatmul), ("where", s_where))}
+        boot_forms = {"d[:,idx64]": g_adv64, "d[:,idx32]": g_adv32}
+        if M == 1:          # at M = 4 torch refused a launch of the row forms ("invalid configuration argument"); cause not looked into
+            boot_forms.update({"dT[idx64]": g_rows64, "dT.index_select(idx32)": g_select32})
+        # bytes of a tile's largest tensors: float64 signs and bits / int64 indices and the M gathered float64 planes
+        sign_bytes, boot_bytes = (lambda t: t * Q * 20.0), (lambda t: t * Q * (8.0 + 8.0 * M))
+
+        def search(forms, tile_bytes, count):
+            """{form: {tile: us per replicate}} and the fastest (us, form, tile)"""
+            table, best = {}, None
+            for name, fn in forms.items():
+                table[name], tile, last = {}, min(first_tile, R), None
+                while True:
+                    n = min(R, 2 * tile)
+
+                    def run(n=n, tile=tile):
+                        acc = torch.zeros(M, device=dev)
+                        for r0 in range(0, n, tile):
+                            acc += count(fn(min(tile, n - r0)))
+                    fn(tile)
+                    torch.cuda.synchronize()
+                    us = timed(run) / n * 1e3
+                    table[name][tile] = us
+                    if best is None or us < best[0]:
+                        best = (us, name, tile)
+                    # a gather is kept below 2^31 gathered elements: beyond it torch's index kernels refuse the launch
+                    if tile >= R or tile_bytes(4 * tile) > TILE_BYTES or (last is not None and us > 0.97 * last) \
+                            or (forms is boot_forms and 4 * tile * Q * M >= 2 ** 31):
+                        break
+                    last, tile = us, min(4 * tile, R)
+                torch.cuda.empty_cache()
+            return table, best
+        s_table, s_best = search(sign_forms, sign_bytes, lambda sg: (sg.abs() >= t_obs.abs()[None, :]).sum(0))
+        b_table, b_best = search(boot_forms, boot_bytes, lambda bt: (bt <= 0).sum(1))
+
+        def composed():
+            ge, le = torch.zeros(M, device=dev), torch.zeros(M, device=dev)
+            for r0 in range(0, R, s_best[2]):
+                ge += (sign_forms[s_best[1]](min(s_best[2], R - r0)).abs() >= t_obs.abs()[None, :]).sum(0)
+            for r0 in range(0, R, b_best[2]):
+                le += (boot_forms[b_best[1]](min(b_best[2], R - r0)) <= 0).sum(1)
+            return ge, le
+        kernel()
+        composed()
+        torch.cuda.synchronize()
+        tk, tc = [], []
+        for _ in range(reps):
+            tk.append(timed(kernel))
+            tc.append(timed(composed))
+        mk, mc = sorted(tk)[reps // 2], sorted(tc)[reps // 2]
+        draws = 2.0 * R * Q
+        print(f"compare Q={Q} M={M} R={R} form={plan['form']} chunks={plan['chunks']} workspace={wsb / 1e6:.1f} MB", flush=True)
+        for title, table, best in (("randomization", s_table, s_best), ("bootstrap", b_table, b_best)):
+            for name, row in table.items():
+                print(f"compare   torch {title:13s} {name:24s} us per replicate at tile " + ", ".join(f"{t}: {v:.3f}" for t, v in row.items()), flush=True)
+            print(f"compare   torch {title:13s} best: {best[1]} at tile {best[2]}, {best[0]:.3f} us per replicate", flush=True)
+        print(f"compare   rlt_paired_compare: {mk:10.3f} ms (min {min(tk):.3f}, max {max(tk):.3f}, {reps} calls)  {draws / mk / 1e6:8.2f} G draws/s", flush=True)
+        print(f"compare   torch composition : {mc:10.3f} ms (min {min(tc):.3f}, max {max(tc):.3f}, {reps} calls)  {draws / mc / 1e6:8.2f} G draws/s"
+              f"   composition / kernel: {mc / mk:.2f}x"
+              + ("  (the kernel is SLOWER than the torch composition here)" if mk > mc else ""), flush=True)
+        del base, sys_, ws, rs, bs, d, dT
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
