@@ -240,6 +240,51 @@ int rlt_cut_report(const float* p, int rule, const float* labels, const float* d
                    double* best_dcg, int32_t* best_dcg_k, int32_t* better, double* hist, double* pred_curve, double* reward_curve,
                    double* sums, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ cut sweep
+ * T threshold cut rules at once from one read of a per-position value array v and of the labels: where on the
+ * effectiveness / cost trade-off a cut operates.  (The reference has no counterpart: it only ever takes the argmax.)
+ *   v          (B,S) fp32 read at element stride v_stride = 1 or 2 (2: the class-0 column of BiCut's (B,S,2) output); S in
+ *              1..1024, B >= 1.
+ *   thresholds T float64 in device memory, 1 <= T <= 64, in any order; 8-byte aligned.
+ *   rule, positions j = 1..S, v widened to float64 before every comparison, a NaN compares false:
+ *     RLT_SWEEP_QUANTILE    v is a cut distribution.  C_j = the float64 inclusive prefix sum of v;
+ *                           k = 1 + #{ j in 1..S-1 : C_j < tau * C_S }, in 1..S: the smallest k whose mass reaches the share tau
+ *                           (tau * C_S is one float64 multiply).  A list whose total is 0 or NaN gets k = 1, because every
+ *                           comparison is false; so does every tau <= 0 on non-negative v.
+ *     RLT_SWEEP_FIRST_BELOW v holds retrieval scores.  k = the number of leading positions with v_j >= tau, in 0..S.  k = 0
+ *                           keeps nothing and every metric of that list is 0: the k = 0 entry of rlt_truncation_curves.
+ *     RLT_SWEEP_FIRST_ABOVE v is a per-position stop probability.  k = the first j with v_j >= tau, S if there is none.
+ * Outputs (either may be NULL, not both):
+ *   k     (B,T) int32: the cut of every list at every threshold;
+ *   curve (RLT_SWEEP_COLS,T) float64, 8-byte aligned: sums over the lists - accumulate = 1 ADDS this batch, 0 overwrites - of
+ *         row 0: k;  1: F1@k;  2: DCG@k with metric_penalty;  3: precision c_k / k (0 at k = 0);  4: recall c_k / N (0 if N = 0);
+ *         5: F_beta = ((1 + beta^2) P) R / (beta^2 P + R), 0 if the denominator is 0;  6: [k == S] (nothing cut);  7: 1 (lists),
+ *         c_k = the number of labels equal to 1 in the first k positions, N = their number in the list.
+ * F1@k is formed from the integers (c_k, N, k) in rlt_cut_metrics_ex's operation order: bit-identical to that entry point for
+ * k >= 1 on 0/1 labels.  DCG@k = sum_{j <= k} (label == 1 ? 1 : metric_penalty) * (the table's 1 / log2(j + 1)) from a prefix scan in position order
+ * (64-lane scans carried across rounds of 64), not rlt_cut_metrics' lane-strided sum: equal to it to float64 rounding, not to
+ * bits.  Rows 0, 6 and 7 are sums of integers and exact below 2^53.  The sums over lists go lane by lane, wavefront by
+ * wavefront, then through one float64 record per workgroup and a fixed-order column reduction.
+ * labels NULL = label-free mode (inference): curve must be NULL and k non-NULL; only the cuts are produced, and dcg_table, ws,
+ * metric_penalty and beta are not read.  (labels with curve NULL does the same.)
+ * dcg_table: as for rlt_loss_metrics.  ws: rlt_cut_sweep_workspace(B, S, T) bytes, 8-byte aligned (0 for B <= 0, S outside
+ * 1..1024 or T outside 1..64; never smaller for a larger B).  Errors before any launch: RLT_E_ARG (v or thresholds NULL,
+ * non-positive B, S or T, rule outside 0..2, v_stride outside {1,2}, both outputs NULL, curve without labels, dcg_table or ws),
+ * RLT_E_SHAPE (S > 1024, T > 64), RLT_E_ALIGN, RLT_E_WORKSPACE.  Two launches (one without curve): the pass - a wavefront owns
+ * whole lists, the count that defines k is taken per threshold over the wavefront, then the T thresholds are finished one lane
+ * each from the count and DCG prefixes in LDS - and the reduction of the records; no atomics, no allocation, no host
+ * synchronisation, bitwise reproducible.  Algorithmic bytes per list: 8 S read (4 S without labels) + 4 T of cuts. */
+#define RLT_SWEEP_QUANTILE    0
+#define RLT_SWEEP_FIRST_BELOW 1
+#define RLT_SWEEP_FIRST_ABOVE 2
+#define RLT_SWEEP_COLS        8
+size_t rlt_cut_sweep_workspace(int B, int S, int T);
+int rlt_cut_sweep(const float* v, int v_stride, int rule, const double* thresholds, int T,
+                  const float* labels, int B, int S, double metric_penalty, double beta,
+                  const void* dcg_table, int accumulate,
+                  int32_t* k /* (B,T) or NULL */, double* curve /* (RLT_SWEEP_COLS,T) or NULL */,
+                  void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ dense contraction (M2-M7)
  * C[M,N] (+)= op(A) * op(B) (+ bias[N] + bias2[N]), optional ReLU.  fp32 in, fp32 accumulate on
  * the f32 MFMA (exact fp32 products, v_mfma_f32_32x32x2_f32).

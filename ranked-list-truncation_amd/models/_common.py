@@ -88,16 +88,25 @@ def pick_tasks(num_tasks):
 class CutModel(nn.Module):
     """Common base of the truncation models: `truncate` says where the model cuts each list, with no labels."""
 
-    def truncate(self, x):
+    def truncate(self, x, *, rule=None, tau=None):
         """x: what forward takes (BiCut with sparse_input: an ops.SparseBatch).  Runs the model in eval mode under no_grad and
         returns (k (B,) int32, p_k (B,) float32) on the device: each list's cut and the winning value (rlt_cut_report, label-free:
-        first maximum + 1, or BiCut's rule on its (B,S,2) output).  The module's train / eval state is restored."""
+        first maximum + 1, or BiCut's rule on its (B,S,2) output).  The module's train / eval state is restored.
+        With `rule` and `tau` set ('quantile' | 'above' | 'score' and one threshold: ops.cut_sweep) the model's output is cut by
+        that rule instead - BiCut's class-0 column at stride 2 - and only k (B,) int32 is returned (rlt_cut_sweep, label-free,
+        T = 1; k may be 0 under 'score')."""
+        if (rule is None) != (tau is None):
+            raise ValueError("truncate: pass both `rule` and `tau`, or neither")
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
                 out = self(x)
                 cut = out[-1] if isinstance(out, (list, tuple)) else out
+                if rule is not None:
+                    thr = torch.full((1,), float(tau), dtype=torch.float64, device=cut.device)
+                    k, _ = ops.cut_sweep(cut, thr, rule)
+                    return k.reshape(-1)
                 per, _ = ops.cut_report(cut)
         finally:
             self.train(was_training)

@@ -20,6 +20,9 @@ GEMM_RELU, GEMM_ACCUMULATE = 1, 2
 HEAD_SOFTMAX, HEAD_SIGMOID, HEAD_IDENTITY = 0, 1, 2
 PROBE_BCE, PROBE_RERANK = 0, 1
 CUT_ARGMAX, CUT_PAIR = 0, 1
+SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE = 0, 1, 2
+SWEEP_COLS, SWEEP_MAX_T = 8, 64
+SWEEP_ROWS = ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut", "n_lists")      # the rows of rlt_cut_sweep's curve
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
 
@@ -52,6 +55,9 @@ _SIGNATURES = {
     "rlt_cut_report_workspace": (c_size_t, [c_int, c_int]),
     "rlt_cut_report": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_float, c_double, c_double, c_double, P, c_int,
                                P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    # threshold cut rules and the effectiveness / cost curve (csrc/sweep.hip)
+    "rlt_cut_sweep_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "rlt_cut_sweep": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_int, c_double, c_double, P, c_int, P, P, P, c_size_t, P]),
     "rlt_probe_heads_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rlt_probe_heads": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
     "rlt_neighbor_features": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_int, c_int, P]),

@@ -1212,6 +1212,64 @@ def cut_report(p, labels=None, metric=N.METRIC_F1, penalty=-1.0, metric_penalty=
     return out, acc
 
 
+SWEEP_RULES = {"quantile": N.SWEEP_QUANTILE, "score": N.SWEEP_FIRST_BELOW, "below": N.SWEEP_FIRST_BELOW,
+               "above": N.SWEEP_FIRST_ABOVE}
+
+
+def sweep_rule(rule):
+    """'quantile' | 'score' ('below') | 'above' | an RLT_SWEEP_* code -> the code."""
+    code = SWEEP_RULES.get(rule, rule)
+    if code not in (N.SWEEP_QUANTILE, N.SWEEP_FIRST_BELOW, N.SWEEP_FIRST_ABOVE):
+        raise ValueError(f"unknown cut rule {rule!r}: one of {sorted(SWEEP_RULES)}")
+    return int(code)
+
+
+def cut_sweep(v, thresholds, rule, labels=None, penalty=-1.0, beta=1.0, curve=None, want_k=True):
+    """T threshold cuts of every list from one pass over v and the labels (rlt_cut_sweep).  v: (B,S) / (B,S,1) values, or
+    BiCut's (B,S,2) output, whose class-0 column is then read at stride 2 without a copy; thresholds: (T,) float64 tensor on
+    the device, 1 <= T <= 64; rule: 'quantile' (v a cut distribution: the smallest k whose mass reaches the share tau),
+    'score' (v retrieval scores: the leading positions with v >= tau, k may be 0) or 'above' (v a stop probability: the first
+    position with v >= tau).  Returns (k (B,T) int32 or None with want_k=False, curve): with labels, curve is the (8,T) float64
+    sums over lists of k, F1@k, DCG@k (with `penalty`), precision, recall, F_beta, [k == S] and 1 (native.SWEEP_ROWS) - pass
+    the tensor of an earlier call back as `curve` and this batch is ADDED into it; without labels it is None (label-free mode:
+    only the cuts).  No host synchronisation."""
+    v = N.f32c(v.detach())
+    N.require_cuda(v, labels, thresholds)
+    if v.dim() == 3 and v.shape[2] == 1:
+        v = v.reshape(v.shape[0], v.shape[1])
+    stride = 2 if v.dim() == 3 and v.shape[2] == 2 else 1
+    if v.dim() != (3 if stride == 2 else 2):
+        raise ValueError(f"cut_sweep: the values must be (B,S), (B,S,1) or (B,S,2); got {tuple(v.shape)}")
+    B, S = v.shape[:2]
+    dev = v.device
+    if thresholds.dtype != torch.float64 or thresholds.dim() != 1 or not thresholds.is_contiguous():
+        raise ValueError("cut_sweep: thresholds must be a contiguous 1-d float64 tensor")
+    T = int(thresholds.numel())
+    if not 1 <= T <= N.SWEEP_MAX_T:
+        raise ValueError(f"cut_sweep: {T} thresholds, outside 1..{N.SWEEP_MAX_T}")
+    code = sweep_rule(rule)
+    if labels is None:
+        if curve is not None or not want_k:
+            raise ValueError("cut_sweep: without labels only the cuts are produced (curve=None, want_k=True)")
+    else:
+        labels = N.f32c(labels)
+        if tuple(labels.shape) != (B, S):
+            raise ValueError(f"cut_sweep: labels {tuple(labels.shape)} do not match the values' {(B, S)}")
+    accumulate = curve is not None
+    if labels is not None and not accumulate:
+        curve = torch.empty((N.SWEEP_COLS, T), dtype=torch.float64, device=dev)
+    elif accumulate and (tuple(curve.shape) != (N.SWEEP_COLS, T) or curve.dtype != torch.float64 or not curve.is_contiguous()):
+        raise ValueError(f"cut_sweep: the accumulator must be a contiguous ({N.SWEEP_COLS},{T}) float64 tensor")
+    k = torch.empty((B, T), dtype=torch.int32, device=dev) if want_k else None
+    ws, ws_bytes = None, 0
+    if labels is not None:
+        ws_bytes = query("rlt_cut_sweep_workspace", B, S, T)
+        ws = workspace(ws_bytes, dev)
+    call("rlt_cut_sweep", ptr(v), stride, code, ptr(thresholds), T, ptr(labels), B, S, float(penalty), float(beta),
+         ptr(dcg_table(dev)) if labels is not None else None, int(accumulate), ptr(k), ptr(curve), ptr(ws), ws_bytes, stream())
+    return k, curve
+
+
 def neighbor_features(doc_ids, table, out=None, col=0, validate=True):
     """AttnCut's neighbour-similarity statistics (rlt_neighbor_features): doc_ids (B,S) int32 rows of `table` in rank order ->
     per position the cosine similarity to the neighbouring documents, the tf-idf column first, then the doc2vec one.

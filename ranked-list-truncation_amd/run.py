@@ -23,6 +23,9 @@ state_dict checkpoint on best test F1, run.py:153-232) and the same log lines.  
   * --draw 1: the arithmetic of the reference's figure (run.py:188,242-298) - the batch-mean softmax of the reward and the
     batch-mean sharpened softmax of the model's output - goes to scalars.jsonl under draw/reward and draw/prediction on the
     reference's condition (even epoch, a batch of more than 40 lists); no image is written;
+  * --cut-sweep RULE:LO:HI:N [--sweep-out PATH]: rank 0 evaluates N thresholds of a cut rule (the predicted-mass quantile, the
+    first output above tau, or the retrieval score falling below tau) on the train and test lists in one fused pass per batch,
+    tunes tau* on train and reports test there beside the argmax cut (utils/sweep.py);
   * not carried over: rendering figures and the hyper-parameter random search.
 """
 import argparse
@@ -377,6 +380,62 @@ class Trainer:
             logging.info('\tCompare: {}'.format(line))
         return lines
 
+    def cut_sweep(self, spec, out_path=None):
+        """--cut-sweep RULE:LO:HI:N (or score:auto:N): per list length of the test split, the train and the test buckets go
+        through one forward each and `CutSweep` (utils/sweep.py); tau* = the first threshold with the best mean of the run's
+        criterion on the train lists.  Logs the test curve and the test figures at tau* beside the argmax cut's, writes
+        everything to `out_path` (.npz, or .json) and returns {length: {...}}.  The 'score' rule reads feature 0 of X and runs no
+        model.  No collective: rank 0 calls it."""
+        import numpy as np
+        from utils.report import CutReport
+        from utils.sweep import CutSweep, score_quantiles
+        rule, thresholds = spec if isinstance(spec, tuple) else parse_cut_sweep(spec)
+        metric = self.args.criterion if self.args.criterion in ("f1", "dcg") else "f1"
+        buckets = {split: {L: (x, y) for L, _q, x, y in self._split_batches(split)} for split in ("train", "test")}
+        results, arrays = {}, {}
+        for L, (x_te, y_te) in buckets["test"].items():
+            if L not in buckets["train"]:
+                logging.info('\tCut sweep (S = {}): no train lists of this length, skipped'.format(L))
+                continue
+            x_tr, y_tr = buckets["train"][L]
+            th = score_quantiles(x_tr[..., 0].cpu().numpy(), thresholds) if isinstance(thresholds, int) else thresholds
+            sweeps = {}
+            argmax = None if rule == "score" else CutReport(L, metric=metric, device=self.device)
+            for split, (x, y) in (("train", (x_tr, y_tr)), ("test", (x_te, y_te))):
+                sw = CutSweep(L, rule, th, device=self.device)
+                for i in range(0, x.shape[0], self.batch_size):
+                    xb, yb = x[i:i + self.batch_size], y[i:i + self.batch_size]
+                    v = xb[..., 0].to(self.device, non_blocking=True) if rule == "score" else self._forward_eval(xb)
+                    sw.update(v, yb)
+                    if argmax is not None and split == "test":
+                        argmax.update(v, yb)
+                sweeps[split] = sw
+            tau, idx, _ = sweeps["train"].best(metric)
+            rec = {"rule": rule, "metric": metric, "tau": tau, "index": idx, "n_train": sweeps["train"].n_lists,
+                   "n_test": sweeps["test"].n_lists, "train": sweeps["train"].at(tau), "test": sweeps["test"].at(tau)}
+            if argmax is not None:
+                summ = argmax.summary()
+                rec["argmax"] = {"f1": summ["f1"], "dcg": summ["dcg"], "k": summ["mean_k"]}
+            for split, sw in sweeps.items():
+                c = sw.curve()
+                arrays[f"thresholds_{L}"] = c["thresholds"]
+                for name in ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut"):
+                    arrays[f"{split}_{name}_{L}"] = c[name]
+                if split == "test":
+                    for t, kk, f1, dcg in zip(c["thresholds"], c["k"], c["f1"], c["dcg"]):
+                        logging.info('\tCut sweep ({} S = {}): tau = {:.6g} | mean k = {:.3f} | f1 = {:.6f} | dcg = {:.6f}'.format(
+                            rule, L, t, kk, f1, dcg))
+            logging.info('\tCut sweep ({} S = {}) at the train-tuned tau* = {:.6g}: test {}{}'.format(
+                rule, L, tau, json.dumps(rec["test"]), ' | argmax cut: {}'.format(json.dumps(rec["argmax"])) if argmax is not None else ''))
+            results[str(L)] = rec
+        if out_path:
+            if out_path.endswith(".json"):
+                with open(out_path, "w") as f:
+                    json.dump({"results": results, "curves": {k: v.tolist() for k, v in arrays.items()}}, f)
+            else:
+                np.savez(out_path, summary=np.asarray(json.dumps(results)), lengths=np.asarray(sorted(map(int, results))), **arrays)
+        return results
+
     def draw(self, epoch):
         """--draw 1 (run.py:188): for every test batch of more than 40 lists, the two curves `Trainer.plot` draws (run.py:262-283,
         tau = 0.9) into the scalar log.  The batches are the test buckets in file order."""
@@ -408,6 +467,8 @@ class Trainer:
                                               bool(getattr(self.args, "report_labels", 1)))
             if getattr(self.args, "compare_to", None):
                 self.compare_lines = self.compare(self.args.report_out, self.args.compare_to)
+        if getattr(self.args, "cut_sweep", None) and self.rank == 0:
+            self.sweep_results = self.cut_sweep(self.args.cut_sweep, getattr(self.args, "sweep_out", None))
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -453,6 +514,15 @@ def log_grad_guard(writer, optimizer, epoch):
     return {tag.split('/', 1)[1]: (v if math.isfinite(v) else None) for tag, v in zip(GRAD_GUARD_TAGS, vals)}
 
 
+def parse_cut_sweep(spec):
+    """argparse type of --cut-sweep: 'RULE:LO:HI:N' or 'score:auto:N' -> (rule, thresholds or N) (utils/sweep.py)."""
+    from utils.sweep import parse_sweep
+    try:
+        return parse_sweep(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Truncation Model Trainer Args (HIP hot path)")
     p.add_argument('--retrieve-data', type=str, default='robust04')
@@ -496,6 +566,13 @@ def build_parser():
                         "(paired randomization test, bootstrap interval, sign and t statistics) and logs one line per file")
     p.add_argument('--report-split', type=str, default='test', choices=('train', 'test'))
     p.add_argument('--report-labels', type=int, default=1, choices=(0, 1), help="0: label-free report (k, winning value, margin only)")
+    p.add_argument('--cut-sweep', type=parse_cut_sweep, default=None, metavar='RULE:LO:HI:N',
+                   help="after training (or with --epochs 0 --ft 1 --model-path CKPT) rank 0 evaluates N thresholds from LO to HI of a "
+                        "cut rule on the train and test lists in one pass each: quantile (the smallest cut whose predicted mass "
+                        "reaches the share tau), above (the first position whose output is >= tau) or score (cut where feature 0 of "
+                        "X, the retrieval score, falls below tau; no model; score:auto:N takes N quantiles of the train scores); "
+                        "logs the test curve and the test figures at the train-tuned tau* beside the argmax cut's")
+    p.add_argument('--sweep-out', type=str, default=None, help="--cut-sweep writes its curves and the tuned figures here (.npz or .json)")
     p.add_argument('--draw', type=int, default=0, choices=(0, 1),
                    help="1: on even epochs, the reward and prediction curves of the reference's figure for every test batch of more "
                         "than 40 lists go to scalars.jsonl (draw/reward, draw/prediction); no image is written")

@@ -3,6 +3,8 @@
   Oracle.ipynb               best_cut(labels): mean over lists of the best F1 / DCG any cut k = 0..S achieves
   Fixed_k.ipynb              fixed_k(labels, k): mean F1 / DCG when every list is cut at k (k or the notebook's [k_f1, k_dcg])
   Greedy_k.ipynb             greedy_k(train, test): the k with the best mean F1 (DCG) on train, applied to test
+  (no notebook)              score_threshold(train, test, thresholds): cut where the retrieval score falls below a threshold
+                             tuned on train - the label-free rule beside Greedy-k (rlt_cut_sweep, FIRST_BELOW)
   Truncation_analysis.ipynb  TruncationCurves.f1_curve() / dcg_curve() (mean over lists for each k = 0..S) and
                              irrelevant_share() (`countp`: share of irrelevant documents in each prefix, k = 1..S)
 
@@ -134,3 +136,20 @@ def greedy_k(train_labels, test_labels, penalty=-1, device=None):
     k_f1, k_dcg = _curves(train_labels, penalty, device).best_k()
     f1, dcg = _curves(test_labels, penalty, device).fixed_k((k_f1, k_dcg))
     return f1, dcg, k_f1, k_dcg
+
+
+def score_threshold(train_scores, train_labels, test_scores, test_labels, thresholds, penalty=-1, device=None):
+    """The tuned score-threshold baseline: every list is cut after its leading positions whose retrieval score is >= theta (a
+    list whose first score is below theta keeps nothing and earns 0).  theta_F1 (theta_DCG) = the first of `thresholds` (at
+    most 64) with the best mean F1 (DCG) on the training split, then the test split's mean F1 (DCG) there.  scores, labels:
+    (B, S) in rank order.  Returns (F1, DCG, theta_F1, theta_DCG)."""
+    from utils.sweep import CutSweep
+    dev = _dev(device)
+    sweeps = []
+    for scores, labels in ((train_scores, train_labels), (test_scores, test_labels)):
+        y = _labels(labels, dev)
+        v = _labels(scores, dev)
+        sweeps.append(CutSweep(y.shape[1], "score", thresholds, penalty, device=dev).update(v, y))
+    train, test = sweeps
+    th_f1, th_dcg = train.best("f1")[0], train.best("dcg")[0]
+    return test.at(th_f1)["f1"], test.at(th_dcg)["dcg"], th_f1, th_dcg

@@ -224,6 +224,86 @@ def report(B=1048576, S=300, reps=9):
     print(f"cut report composed / fused: {mc / mf:.2f}x", flush=True)
 
 
+def sweep(B=1048576, S=300, T=19, reps=9):
+    """rlt_cut_sweep (T threshold cuts and their eight curve rows from one read of p and the labels) against two compositions of
+    what exists without it, on the same data, QUANTILE rule: (a) one float64 cumsum of p, one batched searchsorted for the T
+    targets and T launches of rlt_cut_metrics_ex at k[:, t] - k, F1 and DCG only, precision / recall / F_beta are not available
+    that way; (b) torch alone: the cumsum and searchsorted, float64 cumsums of the relevant count and of the DCG terms, a gather
+    at k and the eight rows as tensor arithmetic.  1,048,576 lists x 300 positions, T = 19 thresholds 0.05..0.95.  HIP events
+    around single alternating launches, the median of `reps`; GB/s on the fused pass's algorithmic bytes, 8 S per list."""
+    g = torch.Generator(device=dev).manual_seed(7)
+    prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+    y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+    p = torch.softmax(torch.randn(B, S, device=dev, generator=g), 1).contiguous()
+    taus = torch.linspace(0.05, 0.95, T, dtype=torch.float64, device=dev)
+    tab = ops.dcg_table(dev)
+    k = torch.zeros(B, T, dtype=torch.int32, device=dev)
+    curve = torch.zeros(N.SWEEP_COLS, T, dtype=torch.float64, device=dev)
+    wsb = N.query("rlt_cut_sweep_workspace", B, S, T)
+    ws = N.workspace(wsb, dev)
+
+    def fused():
+        call("rlt_cut_sweep", ptr(p), 1, N.SWEEP_QUANTILE, ptr(taus), T, ptr(y), B, S, -1.0, 1.0, ptr(tab), 0, ptr(k), ptr(curve),
+             ptr(ws), wsb, stream())
+    kb, f1, dcg, s2 = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.float64, device=dev), \
+        torch.zeros(B, dtype=torch.float64, device=dev), torch.zeros(2, dtype=torch.float64, device=dev)
+    out_a = torch.zeros(3, T, dtype=torch.float64, device=dev)
+
+    def cuts():
+        C = torch.cumsum(p, 1, dtype=torch.float64)
+        target = taus[None, :] * C[:, -1:]
+        return (1 + torch.searchsorted(C[:, :-1].contiguous(), target)).to(torch.int32)
+
+    def composed_metrics():
+        kk = cuts().t().contiguous()
+        for t in range(T):
+            call("rlt_cut_metrics_ex", None, ptr(y), ptr(kk[t]), B, S, -1.0, ptr(kb), ptr(f1), ptr(dcg), ptr(s2), stream())
+            out_a[1:, t] = s2
+        out_a[0] = kk.sum(1, dtype=torch.float64)
+    coef = tab[:S]
+
+    def composed_torch():
+        kk = cuts().long()
+        rel = y == 1.0
+        cnt = torch.cumsum(rel, 1, dtype=torch.float64)
+        dpre = torch.cumsum(torch.where(rel, coef, -coef), 1)
+        hits, d = cnt.gather(1, kk - 1), dpre.gather(1, kk - 1)
+        n = cnt[:, -1:]
+        prec, rec = hits / kk, torch.where(n != 0, hits / n, torch.zeros_like(hits))
+        den = prec + rec
+        f = torch.where(den != 0, 2.0 * prec * rec / den, torch.zeros_like(den))
+        return torch.stack([kk.sum(0, dtype=torch.float64), f.sum(0), d.sum(0), prec.sum(0), rec.sum(0), f.sum(0),
+                            (kk == S).sum(0, dtype=torch.float64), torch.full((T,), float(B), dtype=torch.float64, device=dev)])
+    fns = (("fused", fused), ("cumsum + searchsorted + T x rlt_cut_metrics_ex", composed_metrics), ("torch alone", composed_torch))
+    for _name, fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    # the three agree before anything is timed
+    ref = composed_torch()
+    # (a pair whose target sits within rounding of a prefix may be cut one position apart by another summation order)
+    assert (curve[0] - ref[0]).abs().max() <= 4 and (curve[0] - out_a[0]).abs().max() <= 4 and (curve[6] - ref[6]).abs().max() <= 4
+    for row in (1, 2, 3, 4):
+        assert torch.allclose(curve[row], ref[row], rtol=1e-11, atol=0), row
+    assert torch.allclose(curve[1:3], out_a[1:], rtol=1e-11, atol=0)
+    times = {name: [] for name, _fn in fns}
+    for _ in range(reps):
+        for name, fn in fns:
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[name].append(a.elapsed_time(b))
+    nbytes = 8.0 * B * S
+    med = {name: sorted(v)[reps // 2] for name, v in times.items()}
+    for name, v in times.items():
+        print(f"cut sweep B{B} S{S} T{T} {name:48s}: {med[name] * 1e3:10.1f} us (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f}, {reps} calls)  "
+              f"{nbytes / med[name] / 1e6:8.1f} GB/s on 8 S bytes per list", flush=True)
+    best = min((n for n in med if n != "fused"), key=med.get)
+    print(f"cut sweep best composition: {best}; composition / fused: {med[best] / med['fused']:.2f}x"
+          + ("  (the fused pass is SLOWER than the composition here)" if med["fused"] > med[best] else ""), flush=True)
+
+
 def probe(B=4096, S=300, E=256):
     """rlt_probe_heads (the probing study's fused probe pass) against the composed path on the same data: one BCE and one
     rerank head on frozen position-major features x (S*B, E) = 1.26 GB.  Fused: x read once, no dx.  Composed: rlt_heads_fwd
