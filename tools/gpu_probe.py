@@ -743,7 +743,8 @@ def bicut():
         report(f"bicutloss edge dout {metric}", float(np.abs(o.grad.cpu().numpy() - gold["dout/" + metric]).max()), 1e-6)
     k, _f1, _dcg = Metric.evaluate(torch.softmax(torch.from_numpy(gold["logits"]), dim=2).to(dev), y)
     report("bicut cut rule edge rows", float((k.cpu().numpy() != gold["k_s"]).sum()), 0)
-    # two-class head with dropout: rows still sum to 1, backward matches autograd on the same masks
+    # two-class head: forward and backward against autograd without dropout; with dropout only that the rows still sum to 1 -
+    # the dropout backward and its mask are compared in tests/test_mmoe_bicut_gpu.py (test_pair_softmax, ..._mask_from_the_forward_alone)
     z = torch.randn(6 * 9, 2)
     zd = z.clone().to(dev).requires_grad_(True)
     od = ops.PairSoftmaxFn.apply(zd, 9, 6, 0.0, 0)
