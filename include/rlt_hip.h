@@ -336,6 +336,31 @@ typedef struct rlt_gemm_dispatch {
     int family, ta, tb, fast, persistent, ns, kchunk, slab_xcd, epilogue, narrow;
 } rlt_gemm_dispatch;
 int rlt_gemm_last_dispatch(rlt_gemm_dispatch* out);
+/* What rlt_gemm / rlt_gemm_ex / rlt_gemm_bits decide for one call (csrc/gemm_plan.h: the decision is taken once per call, there;
+ * tests: tests/test_gemm_plan.py, tests/test_gemm_dispatch_gpu.py).  Host only: no device work, no pointers - a call is described by
+ * what the decision may depend on.  `out` is the record rlt_gemm_last_dispatch returns after the real call (family RLT_GEMM_NONE
+ * where that call returns before its launch); the return value is the real call's before its launch: 0, RLT_E_WORKSPACE, or the
+ * -1 of a mask output without RLT_GEMM_RELU on the weights-stationary kernel.  RLT_E_ARG: a null argument, M / N / K <= 0, a leading
+ * dimension below its row, a column sum without ta, an unknown precision code.
+ *   aligned16  bits RLT_GEMM_PTR_A .. _BITS_IN: the pointer is 16-byte aligned (read only for pointers that are present)
+ *   present    bits RLT_GEMM_PTR_BIAS .. _COLSUM: the optional pointer is not NULL
+ *   drop       drop_p > 0
+ *   ws_null, ws_bytes     `ws` is NULL; the bytes the call is given */
+#define RLT_GEMM_PTR_A         1
+#define RLT_GEMM_PTR_B         2
+#define RLT_GEMM_PTR_C         4
+#define RLT_GEMM_PTR_BIAS      8
+#define RLT_GEMM_PTR_BIAS2     16
+#define RLT_GEMM_PTR_BITS_OUT  32
+#define RLT_GEMM_PTR_BITS_IN   64
+#define RLT_GEMM_PTR_RELU_MASK 128
+#define RLT_GEMM_PTR_COLSUM    256
+typedef struct rlt_gemm_call {
+    int ta, tb, M, N, K, lda, ldb, ldc, flags;
+    int aligned16, present, drop, ws_null;
+    size_t ws_bytes;
+} rlt_gemm_call;
+int rlt_gemm_plan(const rlt_gemm_call* call, int precision, rlt_gemm_dispatch* out);
 
 /* The FFN pair of rlt_gemm_ex epilogues with a 1-bit-per-element mask instead of the fp32 activation
  * (nn.TransformerEncoderLayer's linear1 -> ReLU -> dropout forward and the dH = (dY W2) * mask backward):

@@ -180,6 +180,8 @@ __host__ __device__ __forceinline__ bool rlt_keep(uint32_t seed, uint32_t row, u
 // out[col] (+)= sum_{r < R} partial[r * ld + col] for col < ncol; columns >= split go to out1[col - split].
 // One 256-thread workgroup per 16 columns: 16 row lanes x 16 columns, four loads in flight per lane, then a
 // fixed-order LDS reduction over the row lanes (bitwise reproducible).  Launch with grid = cdiv(ncol, 16).
+// (a file that defines RLT_HOST_ONLY before including this header holds no device code and gets no copy of it)
+#ifndef RLT_HOST_ONLY
 static __global__ __launch_bounds__(256) void rlt_rows_reduce_kernel(const float* __restrict__ partial, int R, int ld, int ncol,
                                                                      int split, float* __restrict__ out0,
                                                                      float* __restrict__ out1, int accumulate) {
@@ -208,3 +210,4 @@ static __global__ __launch_bounds__(256) void rlt_rows_reduce_kernel(const float
         *dst = accumulate ? *dst + acc : acc;
     }
 }
+#endif

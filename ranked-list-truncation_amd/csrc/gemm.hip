@@ -11,9 +11,8 @@
 // the tiles an XCD runs are contiguous (they share the A panel in that XCD's L2).
 #include "common.h"
 #include "gemm6s.h"
+#include "gemm_plan.h"
 #include "split6.h"
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -43,12 +42,6 @@ struct GemmArgs {
     const uint32_t* bits_in;   // epilogue mask from such bits: C = bit ? C * mask_scale : 0
     int ldbits;
 };
-
-// rlt_gemm_last_dispatch: called by every launcher right before its launch, with the kernel it is about to start
-inline void note_dispatch(int family, bool ta, bool tb, bool fast, bool persistent, const GemmArgs& g, int ns) {
-    rlt_gemm_dispatch_rec = rlt_gemm_dispatch{family, ta ? 1 : 0, tb ? 1 : 0, fast ? 1 : 0, persistent ? 1 : 0,
-                                              ns, g.kchunk, g.slab_xcd, 0, 0};
-}
 
 // (tile, K slab) of this workgroup.
 //  * no split-K, or a split count that is not a multiple of 8: XCD-aware bijective remap of the flat tile id (the
@@ -937,43 +930,6 @@ __global__ __launch_bounds__(512) void gemm3b_kernel(GemmArgs g) {
     }
 }
 
-// the 256-wide tile needs: split-bf16 mode, M % 256 == 0, N % 256 == 0, whole 32-wide K tiles per slab, the branch-free
-// loader preconditions (16-byte aligned operands, leading dimensions multiples of 4)
-bool gemm_big_ok(const GemmArgs& g, bool ta, bool tb) {
-    static const int off = [] { const char* e = getenv("RLT_GEMM_NO_BIG"); return e ? atoi(e) : 0; }();
-    if (off) return false;
-    if (!g.vecA || !g.vecB) return false;
-    if ((g.M % BM2) || (g.N % BN2) || (g.K % BK3) || (g.kchunk % BK3)) return false;
-    (void)ta; (void)tb;
-    return true;
-}
-template <bool TA, bool TB>
-int launch_gemm3b(GemmArgs g, int ns, hipStream_t st) {
-    const size_t shm = (size_t)2 * 4 * PL2 * sizeof(uint16_t);
-    g.tiles_m = g.M / BM2; g.tiles_n = g.N / BN2;
-    if constexpr (!TA) {
-        // measured: NT -6 % at K = 256, -2 % at K = 2048.  NN (RLT_GEMM_PERSIST_NN=1): -7 % / -2 % alone with a bias epilogue
-        // - once its K loop no longer reloaded a spilled LDS offset (store3b_part: a scratch load in order behind the tile
-        // prefetch had cost +20 %) - but the training step, whose dX products accumulate in place, is 0.4 ms slower with it
-        static const int persist_wgs = [] { const char* e = getenv("RLT_GEMM_PERSIST"); return e ? atoi(e) : 256; }();   // 0: off
-        static const int persist_nn = [] { const char* e = getenv("RLT_GEMM_PERSIST_NN"); return e ? atoi(e) : 0; }();
-        const long long tiles = (long long)g.tiles_m * g.tiles_n;
-        const bool want = TB || (persist_nn && !g.bits_in);
-        if (want && persist_wgs > 0 && ns == 1 && g.K / BK3 >= 2 && tiles > persist_wgs && persist_wgs % 8 == 0) {
-            int rc = rlt_allow_lds(gemm3b_kernel<TA, TB, true>, shm);
-            if (rc) return rc;
-            note_dispatch(RLT_GEMM_3B, TA, TB, true, true, g, ns);
-            hipLaunchKernelGGL((gemm3b_kernel<TA, TB, true>), dim3(persist_wgs), dim3(512), shm, st, g);
-            return RLT_LAUNCH_RESULT();
-        }
-    }
-    int rc = rlt_allow_lds(gemm3b_kernel<TA, TB>, shm);
-    if (rc) return rc;
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    note_dispatch(RLT_GEMM_3B, TA, TB, true, false, g, ns);
-    hipLaunchKernelGGL((gemm3b_kernel<TA, TB>), grid, dim3(512), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
 
 // ======================================================================================================
 // "bf16x6": fp32-FAITHFUL products on the bf16 matrix pipe.  Every fp32 operand is split EXACTLY into three bf16 values,
@@ -1303,17 +1259,6 @@ __global__ __launch_bounds__(512) void gemm6b_kernel(GemmArgs g) {
         }
     }
 }
-template <bool TA, bool TB>
-int launch_gemm6b(GemmArgs g, int ns, hipStream_t st) {
-    const size_t shm = (size_t)6 * PL2 * sizeof(uint16_t);
-    g.tiles_m = g.M / BM2; g.tiles_n = g.N / BN2;
-    int rc = rlt_allow_lds(gemm6b_kernel<TA, TB>, shm);
-    if (rc) return rc;
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    note_dispatch(RLT_GEMM_6B, TA, TB, true, false, g, ns);
-    hipLaunchKernelGGL((gemm6b_kernel<TA, TB>), grid, dim3(512), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
 
 // ======================================================================================================
 // gemm6c: the 256 x 256 six-product tile with the split of the next K tile BEHIND the MFMAs.
@@ -1567,28 +1512,6 @@ __global__ __launch_bounds__(512) void gemm6c_kernel(GemmArgs g) {
         }
     }
 }
-template <bool TA, bool TB>
-int launch_gemm6c(GemmArgs g, int ns, hipStream_t st) {
-    const size_t shm = (size_t)3 * KB6 * sizeof(uint16_t);
-    g.tiles_m = g.M / BM2; g.tiles_n = g.N / BN2;
-    if constexpr (!TA) {
-        static const int persist_wgs = [] { const char* e = getenv("RLT_GEMM6_PERSIST"); return e ? atoi(e) : 256; }();   // 0: off
-        const long long tiles = (long long)g.tiles_m * g.tiles_n;
-        if (persist_wgs > 0 && ns == 1 && tiles > persist_wgs && persist_wgs % 8 == 0) {
-            int rc = rlt_allow_lds(gemm6c_kernel<TA, TB, true>, shm);
-            if (rc) return rc;
-            note_dispatch(RLT_GEMM_6C, TA, TB, true, true, g, ns);
-            hipLaunchKernelGGL((gemm6c_kernel<TA, TB, true>), dim3(persist_wgs), dim3(512), shm, st, g);
-            return RLT_LAUNCH_RESULT();
-        }
-    }
-    int rc = rlt_allow_lds(gemm6c_kernel<TA, TB, false>, shm);
-    if (rc) return rc;
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    note_dispatch(RLT_GEMM_6C, TA, TB, true, false, g, ns);
-    hipLaunchKernelGGL((gemm6c_kernel<TA, TB, false>), grid, dim3(512), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
 
 // ======================================================================================================
 // gemm6e: the 256 x 256 six-product tile by ONE wavefront per SIMD (256 threads, 128 x 128 per wavefront: all 256 AGPRs are
@@ -1660,9 +1583,6 @@ __device__ __forceinline__ void write_output_simple(const GemmArgs& g, const f32
             }
         }
     }
-}
-inline bool gemm6e_epilogue_ok(const GemmArgs& g) {
-    return !g.mask && !g.bits_in && !g.bits_out && g.drop_p <= 0.f;
 }
 
 template <bool TA, bool TB, bool PERSIST>
@@ -1846,62 +1766,6 @@ __global__ __launch_bounds__(256, 1) void gemm6e_kernel(GemmArgs g) {
         }
     }
 }
-template <bool TA, bool TB>
-int launch_gemm6e(GemmArgs g, int ns, hipStream_t st) {
-    const size_t shm = (size_t)3 * KB6 * sizeof(uint16_t);
-    g.tiles_m = g.M / BM2; g.tiles_n = g.N / BN2;
-    if constexpr (!TA) {
-        static const int persist_wgs = [] { const char* e = getenv("RLT_GEMM6_PERSIST"); return e ? atoi(e) : 256; }();   // 0: off
-        const long long tiles = (long long)g.tiles_m * g.tiles_n;
-        if (persist_wgs > 0 && ns == 1 && tiles > persist_wgs && persist_wgs % 8 == 0) {
-            int rc = rlt_allow_lds(gemm6e_kernel<TA, TB, true>, shm);
-            if (rc) return rc;
-            note_dispatch(RLT_GEMM_6E, TA, TB, true, true, g, ns);
-            hipLaunchKernelGGL((gemm6e_kernel<TA, TB, true>), dim3(persist_wgs), dim3(256), shm, st, g);
-            return RLT_LAUNCH_RESULT();
-        }
-    }
-    int rc = rlt_allow_lds(gemm6e_kernel<TA, TB, false>, shm);
-    if (rc) return rc;
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    note_dispatch(RLT_GEMM_6E, TA, TB, true, false, g, ns);
-    hipLaunchKernelGGL((gemm6e_kernel<TA, TB, false>), grid, dim3(256), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
-
-// the bf16x6 tile needs M % 256 == 0, N % 128 == 0, whole 32-wide K tiles per slab and the branch-free loader
-// preconditions; other shapes of that mode run on the exact f32 MFMA kernel (more exact still)
-bool gemm6_ok(const GemmArgs& g) {
-    if (!g.vecA || !g.vecB) return false;
-    return !((g.M % BM6) || (g.N % BN6) || (g.K % BK3) || (g.kchunk % BK3));
-}
-template <bool TA, bool TB>
-int launch_gemm6(GemmArgs g, int ns, hipStream_t st) {
-    const size_t shm = (size_t)2 * BUF6 * sizeof(uint16_t);
-    g.tiles_m = g.M / BM6; g.tiles_n = g.N / BN6;
-    int rc = rlt_allow_lds(gemm6_kernel<TA, TB>, shm);
-    if (rc) return rc;
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    note_dispatch(RLT_GEMM_6, TA, TB, true, false, g, ns);
-    hipLaunchKernelGGL((gemm6_kernel<TA, TB>), grid, dim3(512), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
-
-template <bool TA, bool TB, bool FAST>
-int launch_gemm3_v(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
-    const size_t shm = (size_t)2 * 4 * TILE3 * sizeof(uint16_t);
-    int rc = rlt_allow_lds(gemm3_kernel<TA, TB, FAST>, shm);
-    if (rc) return rc;
-    note_dispatch(RLT_GEMM_3, TA, TB, FAST, false, g, ns);
-    hipLaunchKernelGGL((gemm3_kernel<TA, TB, FAST>), grid, dim3(256), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
-bool gemm_fast_ok(const GemmArgs& g, bool ta, bool tb);
-template <bool TA, bool TB>
-int launch_gemm3(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
-    if (gemm_fast_ok(g, TA, TB)) return launch_gemm3_v<TA, TB, true>(g, grid, ns, st);
-    return launch_gemm3_v<TA, TB, false>(g, grid, ns, st);
-}
 
 // C = sum_z slab[z] (+bias, relu, accumulate); fixed order => deterministic.  Four independent partial sums per
 // element keep four slab loads in flight (the z loop is otherwise one dependent chain of L2/HBM latencies).
@@ -1960,58 +1824,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g, int nspl
             for (; z < nsplit; ++z) c0 += g.cs_slab[(size_t)z * g.M + i];
             g.colsum[i] = (c0 + c1) + (c2 + c3);
         }
-}
-
-template <bool TA, bool TB, int BK, int OCC, bool FAST>
-int launch_gemm_v(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
-    const size_t shm = (size_t)4 * BK * LDT * sizeof(float);
-    int rc = rlt_allow_lds(gemm_kernel<TA, TB, BK, OCC, FAST>, shm);
-    if (rc) return rc;
-    note_dispatch(RLT_GEMM_F32, TA, TB, FAST, false, g, ns);
-    hipLaunchKernelGGL((gemm_kernel<TA, TB, BK, OCC, FAST>), grid, dim3(256), shm, st, g);
-    return RLT_LAUNCH_RESULT();
-}
-// the branch-free loaders need: aligned operands, K % 4 == 0, K-chunks >= 4, MN % 4 == 0 for MN-contiguous operands
-bool gemm_fast_ok(const GemmArgs& g, bool ta, bool tb) {
-    static const int off = [] { const char* e = getenv("RLT_GEMM_NOFAST"); return e ? atoi(e) : 0; }();
-    if (off) return false;
-    if (!g.vecA || !g.vecB || (g.K & 3) || g.K < 4) return false;
-    if (ta && ((g.M & 3) || g.M < 4)) return false;       // A stored [K][M]
-    if (!tb && ((g.N & 3) || g.N < 4)) return false;      // B stored [K][N]
-    return true;
-}
-template <bool TA, bool TB, int BK>
-int launch_gemm(const GemmArgs& g, dim3 grid, int ns, hipStream_t st) {
-    if (gemm_fast_ok(g, TA, TB)) return launch_gemm_v<TA, TB, BK, 4, true>(g, grid, ns, st);
-    return launch_gemm_v<TA, TB, BK, 4, false>(g, grid, ns, st);
-}
-
-// 0 = exact fp32 MFMA (parity mode), 1 = split-bf16 (bf16x3), 2 = fp32-faithful six-product split (bf16x6);
-// RLT_GEMM_MODE overrides the library-wide mode
-int gemm_mode() {
-    static const int forced = [] {
-        const char* e = getenv("RLT_GEMM_MODE");
-        if (!e) return -1;
-        if (!strcmp(e, "bf16x6") || !strcmp(e, "2")) return 2;
-        return (!strcmp(e, "bf16x3") || !strcmp(e, "1")) ? 1 : 0;
-    }();
-    return forced >= 0 ? forced : rlt_precision();
-}
-
-int choose_split(int M, int N, int K) {
-    const long long tiles = (long long)rlt_cdiv(M, BM) * rlt_cdiv(N, BN);
-    // (K from 1024: the reference's own batch sizes - 32 / 63 lists x 300 positions = 9,600 / 18,900 rows - leave the K = 2048 products
-    //  of the encoder with 75-150 output tiles: unsplit, a third of the chip ran 2048-long loops, 160-200 us per product at batch 32)
-    static const int kmin = [] { const char* e = getenv("RLT_GEMM_SPLIT_KMIN"); return e ? atoi(e) : 1024; }();
-    if (tiles >= 256 || K < kmin) return 1;
-    static const int target = [] { const char* e = getenv("RLT_GEMM_SPLIT_TARGET"); return e ? atoi(e) : 1024; }();
-    long long want = target / tiles > 0 ? target / tiles : 1;     // workgroups in flight: a whole number of waves of the grid
-    const long long per = K >= 4096 ? 512 : 256;             // keep >= 512 of K per slice (>= 256 below K = 4096)
-    const long long maxs = K / per > 0 ? K / per : 1;
-    if (want > maxs) want = maxs;
-    if (want > 256) want = 256;
-    if (want >= 8) want = want / 8 * 8;       // whole groups of 8 slabs: one slab per XCD and round (decode_block)
-    return (int)(want < 1 ? 1 : want);
 }
 
 #if defined(RLT_STAMPS)
@@ -2110,9 +1922,40 @@ __global__ __launch_bounds__(256) void narrow_dw_scatter_kernel(const float* __r
 
 int ew_grid(size_t n) { size_t g = (n + 1023) / 1024; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
-}  // namespace
+// gemm_plan.h's per-family table against the kernels' own constants
+constexpr bool family_is(int family, int bm, int bn, size_t lds) {
+    return GEMM_FAMILY[family].bm == bm && GEMM_FAMILY[family].bn == bn && GEMM_FAMILY[family].lds == lds;
+}
+static_assert(family_is(RLT_GEMM_F32, BM, BN, (size_t)4 * 16 * LDT * sizeof(float)) &&
+              family_is(RLT_GEMM_3, BM, BN, (size_t)2 * 4 * TILE3 * sizeof(uint16_t)) &&
+              family_is(RLT_GEMM_3B, BM2, BN2, (size_t)2 * 4 * PL2 * sizeof(uint16_t)) &&
+              family_is(RLT_GEMM_6, BM6, BN6, (size_t)2 * BUF6 * sizeof(uint16_t)) &&
+              family_is(RLT_GEMM_6B, BM2, BN2, (size_t)6 * PL2 * sizeof(uint16_t)) &&
+              family_is(RLT_GEMM_6C, BM2, BN2, (size_t)3 * KB6 * sizeof(uint16_t)) &&
+              family_is(RLT_GEMM_6E, BM2, BN2, (size_t)3 * KB6 * sizeof(uint16_t)), "gemm_plan.h: GEMM_FAMILY");
 
+// (ta, tb) as compile-time tags
+template <typename F>
+int with_layout(bool ta, bool tb, F f) {
+    if (ta) return tb ? f(BoolTag<true>{}, BoolTag<true>{}) : f(BoolTag<true>{}, BoolTag<false>{});
+    return tb ? f(BoolTag<false>{}, BoolTag<true>{}) : f(BoolTag<false>{}, BoolTag<false>{});
+}
+
+// rlt_gemm_last_dispatch: reset to RLT_GEMM_NONE where a call enters gemm_run, set to the plan's record by the launcher right before
+// its launch
 thread_local rlt_gemm_dispatch rlt_gemm_dispatch_rec = {};
+
+// every product kernel of this file: grid, workgroup size and LDS bytes are the plan's
+template <typename Kern>
+int launch(Kern kern, const GemmPlan& p, const GemmArgs& g, hipStream_t st) {
+    const int rc = rlt_allow_lds(kern, p.lds_bytes);
+    if (rc) return rc;
+    rlt_gemm_dispatch_rec = p.d;
+    hipLaunchKernelGGL(kern, dim3(p.grid_x, 1, p.grid_z), dim3(p.wg), p.lds_bytes, st, g);
+    return RLT_LAUNCH_RESULT();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2120,13 +1963,6 @@ int rlt_gemm_last_dispatch(rlt_gemm_dispatch* out) {
     RLT_CHECK_ARG(out);
     *out = rlt_gemm_dispatch_rec;
     return 0;
-}
-
-size_t rlt_gemm_workspace(int ta, int tb, int M, int N, int K) {
-    (void)ta; (void)tb;
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int ns = choose_split(M, N, K);
-    return ns > 1 ? ((size_t)ns * M * N + (size_t)ns * M) * sizeof(float) : 0;
 }
 
 int rlt_gemm(int ta, int tb, int M, int N, int K,
@@ -2138,20 +1974,42 @@ int rlt_gemm(int ta, int tb, int M, int N, int K,
                        0.0f, 0u, ws, ws_bytes, RLT_PRECISION_DEFAULT, stream);
 }
 
+// check the arguments, describe the call, plan (csrc/gemm_plan.hip: every choice, and the family's switches), launch
 static int gemm_run(int ta, int tb, int M, int N, int K,
                     const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     const float* bias, const float* bias2, int flags,
                     const float* relu_mask, int ldmask, float mask_scale, float* colsum_a,
                     float drop_p, uint32_t seed, uint32_t* bits_out, const uint32_t* bits_in,
                     void* ws, size_t ws_bytes, void* stream) {
-    rlt_gemm_dispatch_rec = rlt_gemm_dispatch{};          // RLT_GEMM_NONE until a branch below launches
+    rlt_gemm_dispatch_rec = rlt_gemm_dispatch{};
     RLT_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0);
     RLT_CHECK_ARG(lda >= (ta ? M : K) && ldb >= (tb ? K : N) && ldc >= N);
     RLT_CHECK_ARG(!relu_mask || ldmask >= N);
     RLT_CHECK_ARG(!colsum_a || ta);          // the side column sum needs A stored [K,M]
-    GemmArgs g;
     RLT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
-    g.mask = relu_mask; g.ldmask = ldmask; g.colsum = colsum_a; g.cs_slab = nullptr;
+
+    GemmCall c{};
+    c.ta = ta; c.tb = tb; c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldb = ldb; c.ldc = ldc; c.flags = flags;
+    auto bit = [](bool on, int b) { return on ? b : 0; };
+    c.aligned16 = bit(rlt_aligned16(A), RLT_GEMM_PTR_A) | bit(rlt_aligned16(B), RLT_GEMM_PTR_B) | bit(rlt_aligned16(C), RLT_GEMM_PTR_C) |
+                  bit(rlt_aligned16(bias), RLT_GEMM_PTR_BIAS) | bit(rlt_aligned16(bias2), RLT_GEMM_PTR_BIAS2) |
+                  bit(rlt_aligned16(bits_out), RLT_GEMM_PTR_BITS_OUT) | bit(rlt_aligned16(bits_in), RLT_GEMM_PTR_BITS_IN);
+    c.present = bit(bias, RLT_GEMM_PTR_BIAS) | bit(bias2, RLT_GEMM_PTR_BIAS2) | bit(bits_out, RLT_GEMM_PTR_BITS_OUT) |
+                bit(bits_in, RLT_GEMM_PTR_BITS_IN) | bit(relu_mask, RLT_GEMM_PTR_RELU_MASK) | bit(colsum_a, RLT_GEMM_PTR_COLSUM);
+    c.drop = drop_p > 0.f; c.ws_null = ws == nullptr; c.ws_bytes = ws_bytes;
+
+    const GemmPlan p = gemm_plan(c);
+    if (p.rc) return p.rc;
+
+    hipStream_t st = rlt_stream(stream);
+    if (p.d.family == RLT_GEMM_6S) {
+        const Gemm6sArgs s6{A, B, C, bias, bias2, M, N, K, lda, ldb, ldc, bits_out, bits_in, mask_scale};
+        const int rc = rlt_gemm6s_launch(s6, p, &rlt_gemm_dispatch_rec, st);
+        return rc ? rc : RLT_LAUNCH_RESULT();
+    }
+    const int ns = p.d.ns;
+    GemmArgs g;
+    g.mask = relu_mask; g.ldmask = ldmask; g.colsum = colsum_a;
     g.bits_out = bits_out; g.bits_in = bits_in; g.ldbits = N;
     g.mask_scale = mask_scale; g.drop_p = drop_p; g.drop_thr = rlt_drop_threshold(drop_p); g.seed = seed;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.bias2 = bias2;
@@ -2159,79 +2017,34 @@ static int gemm_run(int ta, int tb, int M, int N, int K,
     g.vecA = (lda % 4 == 0) && rlt_aligned16(A);
     g.vecB = (ldb % 4 == 0) && rlt_aligned16(B);
     g.flags = flags;
-    g.tiles_m = rlt_cdiv(M, BM); g.tiles_n = rlt_cdiv(N, BN);
-    int ns = (bits_out || bits_in) ? 1 : choose_split(M, N, K);       // the bit epilogues live in the GEMM kernel proper
-    if (ns > 1 && (!ws || ws_bytes < ((size_t)ns * M * N + (size_t)ns * M) * sizeof(float))) {
-        if (ws == nullptr && ws_bytes == 0) ns = 1; else return RLT_E_WORKSPACE;
-    }
-    int kchunk = rlt_cdiv(rlt_cdiv(K, ns), 32) * 32;
-    ns = rlt_cdiv(K, kchunk);
-    g.kchunk = kchunk;
-    static const bool no_slab_xcd = getenv("RLT_GEMM_NO_SLAB_XCD") != nullptr;
-    g.slab_xcd = (ns > 1 && ns % 8 == 0 && !no_slab_xcd) ? 1 : 0;
+    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+    g.kchunk = p.d.kchunk;
+    g.slab_xcd = p.d.slab_xcd;
     g.slab = ns > 1 ? (float*)ws : nullptr;
     g.cs_slab = (ns > 1 && colsum_a) ? (float*)ws + (size_t)ns * M * N : nullptr;
-    hipStream_t st = rlt_stream(stream);
-    dim3 grid(g.tiles_m * g.tiles_n * (g.slab_xcd ? ns : 1), 1, g.slab_xcd ? 1 : ns);
-    int rc = 0;
-    // K = 256 with the long dimension in M (the Linear layers of the encoder, the LSTM input projection): the weights-stationary
-    // streaming kernel (csrc/gemm6s.hip) - no K loop, nothing re-split per tile
-    if (gemm_mode() == 2 && !ta && ns == 1 && !relu_mask && !colsum_a && drop_p == 0.f && !(flags & RLT_GEMM_ACCUMULATE) &&
-        (!bits_in || (!bias && !bias2 && !(flags & RLT_GEMM_RELU)))) {
-        const Gemm6sArgs s6{A, B, C, bias, bias2, M, N, K, lda, ldb, ldc, bits_out, bits_in, mask_scale};
-        if (rlt_gemm6s_ok(s6)) {
-            rc = rlt_gemm6s_launch(s6, tb != 0, (flags & RLT_GEMM_RELU) != 0, stream);
-            return rc ? rc : RLT_LAUNCH_RESULT();
+    const int rc = with_layout(ta, tb, [&](auto TA, auto TB) {
+        constexpr bool A_ = decltype(TA)::value, B_ = decltype(TB)::value;
+        auto go = [&](auto kern) { return launch(kern, p, g, st); };
+        const bool persistent = !A_ && p.d.persistent;       // (the persistent forms exist for A stored [M][K] only)
+        switch (p.d.family) {
+        case RLT_GEMM_6E:
+            if constexpr (!A_) if (persistent) return go(gemm6e_kernel<A_, B_, true>);
+            return go(gemm6e_kernel<A_, B_, false>);
+        case RLT_GEMM_6C:
+            if constexpr (!A_) if (persistent) return go(gemm6c_kernel<A_, B_, true>);
+            return go(gemm6c_kernel<A_, B_, false>);
+        case RLT_GEMM_3B:
+            if constexpr (!A_) if (persistent) return go(gemm3b_kernel<A_, B_, true>);
+            return go(gemm3b_kernel<A_, B_>);
+        case RLT_GEMM_6B: return go(gemm6b_kernel<A_, B_>);
+        case RLT_GEMM_6: return go(gemm6_kernel<A_, B_>);
+        case RLT_GEMM_3: return p.d.fast ? go(gemm3_kernel<A_, B_, true>) : go(gemm3_kernel<A_, B_, false>);
+        case RLT_GEMM_F32: return p.d.fast ? go(gemm_kernel<A_, B_, 16, 4, true>) : go(gemm_kernel<A_, B_, 16, 4, false>);
         }
-    }
-    static const bool x6_small_only = getenv("RLT_GEMM6_SMALL") != nullptr;      // A/B switch: 256 x 128 tiles everywhere
-    static const bool x6_no_c = [] { const char* e = getenv("RLT_GEMM6C"); return e && atoi(e) == 0; }();   // A/B switch: RLT_GEMM6C=0 -> gemm6b
-    if (gemm_mode() == 2 && gemm6_ok(g) && g.N % BN2 == 0 && !x6_small_only && !x6_no_c && g.kchunk / BK3 >= 2 &&
-        (min(g.K, g.kchunk) / BK3) >= 2 && (g.K % g.kchunk == 0 || (g.K % g.kchunk) / BK3 >= 2)) {
-        // (every K slab holds at least two K tiles of 32: the k-step pipeline stages one register tile ahead)
-        static const bool x6_e = [] { const char* e = getenv("RLT_GEMM6E"); return !e || atoi(e) != 0; }();     // RLT_GEMM6E=0 -> gemm6c
-        // gemm6e (one wavefront per SIMD) where the K loop decides - the weight-gradient products (A stored [K][M], K = the 1.2 M
-        // rows: 5.66 against 6.38 ms for 2048 x 256 x 1,228,800) and K >= 1024 (ffn1 dX 5.92 against 6.34 ms, ffn2 forward 5.90 against
-        // 6.04) - and the epilogue is one of its plain forms; the K = 256 products (prologue / epilogue bound: 7.02 against 6.70 ms
-        // for 1,228,800 x 2048 x 256) and the mask / dropout epilogues stay on gemm6c.  RLT_GEMM6E_ALL=1: every shape (A/B switch)
-        static const bool x6_e_all = [] { const char* e = getenv("RLT_GEMM6E_ALL"); return e && atoi(e) != 0; }();
-        if (x6_e && gemm6e_epilogue_ok(g) && (ta || g.K >= 1024 || x6_e_all)) {
-            if (!ta && tb) rc = launch_gemm6e<false, true>(g, ns, st);
-            else if (!ta && !tb) rc = launch_gemm6e<false, false>(g, ns, st);
-            else if (!tb) rc = launch_gemm6e<true, false>(g, ns, st);
-            else rc = launch_gemm6e<true, true>(g, ns, st);
-        } else if (!ta && tb) rc = launch_gemm6c<false, true>(g, ns, st);
-        else if (!ta && !tb) rc = launch_gemm6c<false, false>(g, ns, st);
-        else if (ta && !tb) rc = launch_gemm6c<true, false>(g, ns, st);
-        else rc = launch_gemm6c<true, true>(g, ns, st);
-    } else if (gemm_mode() == 2 && gemm6_ok(g) && g.N % BN2 == 0 && !x6_small_only) {
-        if (!ta && tb) rc = launch_gemm6b<false, true>(g, ns, st);
-        else if (!ta && !tb) rc = launch_gemm6b<false, false>(g, ns, st);
-        else if (ta && !tb) rc = launch_gemm6b<true, false>(g, ns, st);
-        else rc = launch_gemm6b<true, true>(g, ns, st);
-    } else if (gemm_mode() == 2 && gemm6_ok(g)) {
-        if (!ta && tb) rc = launch_gemm6<false, true>(g, ns, st);
-        else if (!ta && !tb) rc = launch_gemm6<false, false>(g, ns, st);
-        else if (ta && !tb) rc = launch_gemm6<true, false>(g, ns, st);
-        else rc = launch_gemm6<true, true>(g, ns, st);
-    } else if (gemm_mode() == 1 && gemm_big_ok(g, ta, tb)) {
-        if (!ta && tb) rc = launch_gemm3b<false, true>(g, ns, st);
-        else if (!ta && !tb) rc = launch_gemm3b<false, false>(g, ns, st);
-        else if (ta && !tb) rc = launch_gemm3b<true, false>(g, ns, st);
-        else rc = launch_gemm3b<true, true>(g, ns, st);
-    } else if (gemm_mode() == 1) {
-        if (!ta && tb) rc = launch_gemm3<false, true>(g, grid, ns, st);
-        else if (!ta && !tb) rc = launch_gemm3<false, false>(g, grid, ns, st);
-        else if (ta && !tb) rc = launch_gemm3<true, false>(g, grid, ns, st);
-        else rc = launch_gemm3<true, true>(g, grid, ns, st);
-    } else {
-        if (!ta && tb) rc = launch_gemm<false, true, 16>(g, grid, ns, st);
-        else if (!ta && !tb) rc = launch_gemm<false, false, 16>(g, grid, ns, st);
-        else if (ta && !tb) rc = launch_gemm<true, false, 16>(g, grid, ns, st);
-        else rc = launch_gemm<true, true, 16>(g, grid, ns, st);
-    }
+        return (int)RLT_E_ARG;
+    });
     if (rc) return rc;
-    if (ns > 1)
+    if (p.reduce)
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(ew_grid((size_t)M * N)), dim3(256), 0, st, g, ns);
     return RLT_LAUNCH_RESULT();
 }

@@ -2,7 +2,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include "../../include/rlt_hip.h"
+#include <hip/hip_runtime.h>
+#include "gemm_plan.h"
 
 struct Gemm6sArgs {
     const float* A; const float* B; float* C;      // C[M x N] = A[M x 256] op(B) (+ bias + bias2)
@@ -13,10 +14,9 @@ struct Gemm6sArgs {
     const uint32_t* bits_in;                       // C = bit ? C * mask_scale : 0
     float mask_scale;
 };
-// shape / alignment conditions: K == 256 with N % 256 == 0, or K == 128 with N % 256 == 0 (N % 128 == 0 without the mask epilogues); M >= 8192.
+// Shape / alignment conditions: the gemm6s row of gemm_plan() (csrc/gemm_plan.hip).
 // Mask epilogue (bits_out): the rows past M of the last 32-row block are evaluated as relu(bias) > 0 and their bits land in the final
 // mask word - no consumer reads them (rlt_gemm_bits indexes rows < M), but the word differs from the tiled kernels' (which write 0 there).
-bool rlt_gemm6s_ok(const Gemm6sArgs& g);
-int rlt_gemm6s_launch(const Gemm6sArgs& g, bool tb, bool relu, void* stream);      // 0 or a hip error code (bits_out needs relu; not both bit pointers)
-// the record rlt_gemm_last_dispatch returns: written by the branch that launches (gemm_run, rlt_gemm6s_launch), host only
-extern thread_local rlt_gemm_dispatch rlt_gemm_dispatch_rec;
+// Launches the instantiation the plan names with the plan's grid and LDS bytes and writes p.d to *rec right before the launch.  0 or a
+// hip error code.
+int rlt_gemm6s_launch(const Gemm6sArgs& g, const GemmPlan& p, rlt_gemm_dispatch* rec, hipStream_t st);

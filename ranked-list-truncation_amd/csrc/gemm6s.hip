@@ -14,7 +14,6 @@
 // One barrier per block.  Row bounds are buffer bounds (rows past M are never loaded or stored).
 #include "common.h"
 #include "gemm6s.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -287,38 +286,30 @@ __global__ __launch_bounds__(256, 1) void gemm6s_kernel(Gemm6sArgs g) {
 
 }  // namespace
 
-bool rlt_gemm6s_ok(const Gemm6sArgs& g) {
-    static const bool on = [] { const char* e = getenv("RLT_GEMM6S"); return !e || atoi(e) != 0; }();      // RLT_GEMM6S=0: the tiled kernels (A/B runs)
-    return on && (g.K == 256 || g.K == 128) && (g.N % 256 == 0 || (g.K == 128 && g.N % 128 == 0 && !g.bits_out && !g.bits_in)) && g.N <= 256 * 256 && g.M >= 32 * 256 && g.lda % 4 == 0 && g.ldb % 4 == 0 && g.ldc % 4 == 0 &&
-           rlt_aligned16(g.A) && rlt_aligned16(g.B) && rlt_aligned16(g.C) && (!g.bias || rlt_aligned16(g.bias)) &&
-           (!g.bias2 || rlt_aligned16(g.bias2)) && (size_t)g.lda * 4 * 32 < (1u << 31) && (size_t)g.ldc * 4 * 32 < (1u << 31) &&
-           !(g.bits_out && g.bits_in) && (!g.bits_out || rlt_aligned16(g.bits_out)) && (!g.bits_in || rlt_aligned16(g.bits_in));
-}
+static_assert(gs_lds<8>() == GEMM6S_LDS_K256 && gs_lds<4>() == GEMM6S_LDS_K128, "gemm_plan.h: the LDS bytes of the streaming kernels");
 
-int rlt_gemm6s_launch(const Gemm6sArgs& g, bool tb, bool relu, void* stream) {
-    const bool narrow = g.N % 256 != 0;              // 128-column panels (K = 128)
-    const int npanel = g.N / (narrow ? 128 : 256);
-    const int nblk = (g.M + 31) / 32;
-    int nstream = 256 / npanel;                      // one workgroup per CU: the panels x as many row streams as fill the chip
-    if (nstream < 1) nstream = 1;
-    if (nstream > nblk) nstream = nblk;
-    const size_t lds = g.K == 256 ? gs_lds<8>() : gs_lds<4>();
-    const int epi = g.bits_in ? 3 : g.bits_out ? 2 : relu ? 1 : 0;
+// the instantiation the plan names: K (256 / 128), 128- or 256-column panels, the weight layout, the epilogue code
+int rlt_gemm6s_launch(const Gemm6sArgs& g, const GemmPlan& p, rlt_gemm_dispatch* rec, hipStream_t st) {
+    const int epi = p.d.epilogue;
     auto go = [&](auto kern) {
-        const int rc = rlt_allow_lds(kern, lds);
+        const int rc = rlt_allow_lds(kern, p.lds_bytes);
         if (rc) return rc;
-        rlt_gemm_dispatch_rec = rlt_gemm_dispatch{RLT_GEMM_6S, 0, tb ? 1 : 0, 1, 0, 1, g.K, 0, epi, narrow ? 1 : 0};
-        hipLaunchKernelGGL(kern, dim3(npanel * nstream), dim3(256), lds, rlt_stream(stream), g);
+        *rec = p.d;
+        hipLaunchKernelGGL(kern, dim3(p.grid_x), dim3(p.wg), p.lds_bytes, st, g);
         return 0;
     };
-    if (g.bits_out && !relu) return -1;
-    if (narrow) {
-        if (g.K != 128 || epi >= 2) return -1;
-        return tb ? (epi ? go(gemm6s_kernel<4, 2, true, 1>) : go(gemm6s_kernel<4, 2, true, 0>))
-                  : (epi ? go(gemm6s_kernel<4, 2, false, 1>) : go(gemm6s_kernel<4, 2, false, 0>));
-    }
-#define GS_GO(KS_) (tb ? (epi == 3 ? go(gemm6s_kernel<KS_, 4, true, 3>) : epi == 2 ? go(gemm6s_kernel<KS_, 4, true, 2>) : epi == 1 ? go(gemm6s_kernel<KS_, 4, true, 1>) : go(gemm6s_kernel<KS_, 4, true, 0>)) \
-                       : (epi == 3 ? go(gemm6s_kernel<KS_, 4, false, 3>) : epi == 2 ? go(gemm6s_kernel<KS_, 4, false, 2>) : epi == 1 ? go(gemm6s_kernel<KS_, 4, false, 1>) : go(gemm6s_kernel<KS_, 4, false, 0>)))
-    return g.K == 256 ? GS_GO(8) : GS_GO(4);
-#undef GS_GO
+    auto by_epilogue = [&](auto KS, auto TB) {
+        constexpr int KS_ = decltype(KS)::value;
+        constexpr bool TB_ = decltype(TB)::value;
+        return epi == 3 ? go(gemm6s_kernel<KS_, 4, TB_, 3>) : epi == 2 ? go(gemm6s_kernel<KS_, 4, TB_, 2>)
+             : epi == 1 ? go(gemm6s_kernel<KS_, 4, TB_, 1>) : go(gemm6s_kernel<KS_, 4, TB_, 0>);
+    };
+    const std::integral_constant<int, 8> K256;
+    const std::integral_constant<int, 4> K128;
+    const bool k256 = p.d.kchunk == 256;              // (one slab: the plan's K per slab is K)
+    if (p.d.narrow)                                   // 128-column panels: the plan's row holds K = 128 and the plain epilogues only
+        return p.d.tb ? (epi ? go(gemm6s_kernel<4, 2, true, 1>) : go(gemm6s_kernel<4, 2, true, 0>))
+                      : (epi ? go(gemm6s_kernel<4, 2, false, 1>) : go(gemm6s_kernel<4, 2, false, 0>));
+    if (p.d.tb) return k256 ? by_epilogue(K256, std::true_type{}) : by_epilogue(K128, std::true_type{});
+    return k256 ? by_epilogue(K256, std::false_type{}) : by_epilogue(K128, std::false_type{});
 }

@@ -72,6 +72,7 @@ _SIGNATURES = {
     "rlt_gemm_ex": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, P, c_int, c_float,
                             P, c_float, c_uint32, P, c_size_t, c_int, P]),
     "rlt_gemm_last_dispatch": (c_int, [P]),
+    "rlt_gemm_plan": (c_int, [P, c_int, P]),
     "rlt_dropout_mask": (c_int, [c_uint32, c_size_t, c_int, c_float, P, P]),
     "rlt_attention_dropout_mask": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
     "rlt_attention_dropout_mask_range": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
@@ -179,6 +180,32 @@ def gemm_last_dispatch():
     out = {f: int(getattr(d, f)) for f in GEMM_DISPATCH_FIELDS}
     out["family"] = GEMM_FAMILIES[out["family"]]
     return out
+
+
+GEMM_PTRS = ("A", "B", "C", "bias", "bias2", "bits_out", "bits_in", "relu_mask", "colsum")      # bits of RLT_GEMM_PTR_*
+GEMM_CALL_INTS = ("ta", "tb", "M", "N", "K", "lda", "ldb", "ldc", "flags", "aligned16", "present", "drop", "ws_null")
+
+
+class GemmCall(ctypes.Structure):
+    """rlt_gemm_call: what the GEMM dispatch may depend on - no pointers."""
+    _fields_ = [(f, c_int) for f in GEMM_CALL_INTS] + [("ws_bytes", c_size_t)]
+
+
+def gemm_call(ta, tb, M, N, K, lda=None, ldb=None, ldc=None, flags=0, present=(), misaligned=(), drop=False, ws_bytes=None):
+    """-> GemmCall.  Leading dimensions default to the packed ones; present / misaligned: names of GEMM_PTRS (A, B, C are always
+    present); ws_bytes: None = no workspace (NULL, 0 bytes), else the bytes of a non-null one."""
+    bit = lambda names: sum(1 << GEMM_PTRS.index(n) for n in names)
+    return GemmCall(ta, tb, M, N, K, lda or (M if ta else K), ldb or (K if tb else N), ldc or N, flags,
+                    bit(GEMM_PTRS[:7]) & ~bit(misaligned), bit(present), int(bool(drop)), int(ws_bytes is None), ws_bytes or 0)
+
+
+def gemm_plan(call, precision=PRECISION_DEFAULT):
+    """-> (return code of the real call before its launch, dict of GEMM_DISPATCH_FIELDS as gemm_last_dispatch gives it)."""
+    d = GemmDispatch()
+    rc = load().rlt_gemm_plan(ctypes.byref(call), precision, ctypes.byref(d))
+    out = {f: int(getattr(d, f)) for f in GEMM_DISPATCH_FIELDS}
+    out["family"] = GEMM_FAMILIES[out["family"]]
+    return rc, out
 
 
 ATTN_KERNELS = ("none", "f32", "f32_sb", "f32_occ1", "f32_hd16", "x3", "x6", "x6_img", "x6_pp", "x6_pp_img", "x6_dkv1", "x6_dq1",
