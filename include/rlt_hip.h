@@ -135,6 +135,61 @@ int rlt_loss_metrics(const float* p, const float* labels, const float* dcg_coef,
                      int32_t* k_out, double* f1_out, double* dcg_out, double* sums,
                      const void* dcg_table, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ reward losses for any cut reward (csrc/reward_any.hip)
+ * The reward r[b,k] - the value of cutting list b after position k, k = 1..S - as an ARGUMENT: a spec whose reward is built
+ * from the labels in registers, or a (B,S) matrix the caller supplies.  The F1 / DCG entry points above are not touched.
+ *
+ * rlt_reward_spec is a HOST struct, read at call time; its scalars travel as kernel arguments.
+ *   grade g_j: the label rounded to the nearest integer and clamped to 0..n_grades-1; NaN gives 0.
+ *   RLT_REWARD_FBETA: a document is relevant iff label >= 1; c_k = relevant documents among the first k, N = in the list;
+ *     r_k = (1 + beta^2) c_k / (beta^2 N + k), 0 when c_k == 0 (F_beta of precision c_k / k and recall c_k / N).
+ *   RLT_REWARD_GAIN: cum_k = sum_{j<=k} gain[g_j] d_j, a float64 prefix sum; r_k = cum_k, or with `normalize`
+ *     r_k = cum_k / ideal (0 when ideal <= 0), ideal = sum_g gain[g] (D[a_g + n_g] - D[a_g]) over the grades of positive gain in
+ *     descending gain (ties: the higher grade first), n_g = the list's documents of grade g, a_g = those of the grades taken
+ *     before it, D = the float64 prefix sum of d: the value of the list sorted by gain, which is the largest value of any
+ *     ordering when d is non-negative and non-increasing.  gain = {penalty, 1} with discount == NULL is Metric_for_Loss.dcg.
+ *   Both are formed in float64 and rounded to fp32 once.
+ * Graded labels enter through THIS interface only: the F1 / DCG kernels above test label == 1, where a grade 2 reads as
+ * non-relevant.
+ *
+ * rlt_reward_spec_matrix: r_out and / or q_out = softmax(r / tau) as (B,S) fp32 (the counterpart of rlt_reward_matrix_ex).
+ * rlt_reward_any_loss: the loss of rlt_reward_loss_ex (kind RLT_LOSS_*, the same definitions and / B scaling) on that reward.
+ *   Exactly one reward source: labels + spec (the reward is never written), or r_in, (B,S) fp32, assumed finite and not checked
+ *   (labels and spec NULL); anything else RLT_E_ARG.  q = softmax(r / tau) with the row maximum subtracted; q, the loss terms
+ *   and dp are formed in float64 and rounded to fp32 where they are stored.  dp (B,S) may be NULL.  Per-list outputs, each
+ *   may be NULL: loss_per_list fp32; k_out int32 = first maximum of p, plus 1; r_k fp32 = the reward at that cut; r_best fp32
+ *   and best_k int32 = the row's largest reward over k = 1..S and its first position.  sums: 4 float64 or NULL = sum r_k, sum
+ *   r_best, the number of lists with r_k == r_best, B.  loss_out (or NULL) = (sum of the per-list terms) / B from a float64 sum.
+ *   dcg_table: as for rlt_loss_metrics; read only by a GAIN spec with discount == NULL (may be NULL otherwise).
+ *   ws: rlt_reward_any_workspace(B) bytes, 8-byte aligned (0 for B <= 0; never smaller for a larger B).
+ * Layout as rlt_loss_metrics: a wavefront owns whole lists, four, two or one by S and S % 4; rows of S % 4 == 0 floats are read
+ * and written 16 bytes at a time, so p, labels, r_in, dp, r_out and q_out must then be 16-byte aligned (RLT_E_ALIGN).  S in
+ * 1..1024 (RLT_E_SHAPE beyond).  Two launches: the pass (every workgroup leaves one float64 record in ws) and a one-workgroup
+ * fixed-order reduction.  No atomics, no allocation, no host synchronisation: two calls give the same bits.  Errors before any
+ * launch: RLT_E_ARG (p, ws or both / neither reward source; non-positive B or S; kind or family outside their codes; beta <= 0;
+ * n_grades outside 2..8; a non-finite gain; tau <= 0; a GAIN spec with neither discount nor dcg_table), RLT_E_SHAPE,
+ * RLT_E_ALIGN, RLT_E_WORKSPACE.
+ * Algorithmic bytes per list: read 8 S, write dp 4 S + up to 20 B of results. */
+#define RLT_REWARD_FBETA 0
+#define RLT_REWARD_GAIN  1
+#define RLT_REWARD_MAX_GRADES 8
+typedef struct {
+    int   family;       /* RLT_REWARD_*                                                        */
+    int   n_grades;     /* GAIN: 2..8                                                          */
+    int   normalize;    /* GAIN: 1 = divide by the list's ideal value                          */
+    float beta;         /* FBETA: > 0                                                          */
+    float gain[RLT_REWARD_MAX_GRADES];   /* GAIN: gain of a document of grade g                */
+    const float* discount;               /* GAIN: device, S floats d_j, or NULL = 1/log2(j+2)
+                                            taken from dcg_table                               */
+} rlt_reward_spec;
+int rlt_reward_spec_matrix(const float* labels, int B, int S, const rlt_reward_spec* spec, float tau, const void* dcg_table,
+                           float* r_out, float* q_out, void* stream);
+size_t rlt_reward_any_workspace(int B);
+int rlt_reward_any_loss(const float* p, const float* labels, const rlt_reward_spec* spec, const float* r_in, int B, int S,
+                        int kind, float tau, float* loss_per_list, float* loss_out, float* dp,
+                        int32_t* k_out, float* r_k, float* r_best, int32_t* best_k, double* sums,
+                        const void* dcg_table, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ multi-task terms (L7-L8)
  * utils/losses.py:99-141 (RerankLoss) and nn.BCELoss of :177,:187 (MtCutLoss).
  * rlt_mt_terms: one pass over the rerank scores and/or class probabilities (either may be NULL)

@@ -22,6 +22,7 @@ PROBE_BCE, PROBE_RERANK = 0, 1
 CUT_ARGMAX, CUT_PAIR = 0, 1
 SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE = 0, 1, 2
 SWEEP_COLS, SWEEP_MAX_T = 8, 64
+REWARD_FBETA, REWARD_GAIN, REWARD_MAX_GRADES = 0, 1, 8
 SWEEP_ROWS = ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut", "n_lists")      # the rows of rlt_cut_sweep's curve
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
@@ -40,6 +41,10 @@ _SIGNATURES = {
     "rlt_dcg_table_bytes": (c_size_t, []),
     "rlt_dcg_table_init": (c_int, [P, c_size_t, P]),
     "rlt_loss_metrics": (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_int, c_float, c_double, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    # reward losses for any cut reward (csrc/reward_any.hip)
+    "rlt_reward_spec_matrix": (c_int, [P, c_int, c_int, P, c_float, P, P, P, P]),
+    "rlt_reward_any_workspace": (c_size_t, [c_int]),
+    "rlt_reward_any_loss": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_cut_metrics_ex": (c_int, [P, P, P, c_int, c_int, c_double, P, P, P, P, P]),
     "rlt_mt_terms_workspace": (c_size_t, [c_int, c_int]),
     "rlt_mt_terms": (c_int, [P, P, P, c_int, c_int, c_float, P, P, c_size_t, P]),
@@ -302,6 +307,23 @@ def lstm_ptrs(layers):
         arr[i].b_ih[0], arr[i].b_ih[1] = bif.data_ptr(), bir.data_ptr()
         arr[i].b_hh[0], arr[i].b_hh[1] = bhf.data_ptr(), bhr.data_ptr()
     return arr
+
+
+class RewardSpecStruct(ctypes.Structure):
+    """rlt_reward_spec of include/rlt_hip.h: a host struct, read by the library at call time."""
+    _fields_ = [("family", c_int), ("n_grades", c_int), ("normalize", c_int), ("beta", c_float),
+                ("gain", c_float * REWARD_MAX_GRADES), ("discount", c_void_p)]
+
+
+def reward_spec_struct(family, beta=1.0, gains=(), normalize=False, discount=None):
+    """-> RewardSpecStruct.  `discount`: a device tensor of S floats, or None for the 1 / log2(j + 2) of the DCG table; the
+    caller keeps it alive for the call."""
+    s = RewardSpecStruct()
+    s.family, s.n_grades, s.normalize, s.beta = int(family), len(gains), int(bool(normalize)), float(beta)
+    for i, g in enumerate(gains[:REWARD_MAX_GRADES]):
+        s.gain[i] = float(g)
+    s.discount = None if discount is None else discount.data_ptr()
+    return s
 
 
 def byte_buffer(nbytes, device):

@@ -917,6 +917,56 @@ class RewardLossFn(Function):
         return g.view(ctx.pshape), None, None, None, None, None, None, None
 
 
+class RewardAnyLossFn(Function):
+    """RewardLossFn for any cut reward (rlt_reward_any_loss): `spec`, an object whose `native(S, device)` returns the
+    rlt_reward_spec struct (utils.rewards.RewardSpec), builds the reward from `labels` in registers; or `r`, a (B,S) reward
+    matrix the caller supplies (labels and spec None).  Returns a 0-d loss; with `with_stats` (loss, k (B) int32, stats) where
+    stats = {"r_k", "r_best" (B) fp32, "best_k" (B) int32, "sums" (4) float64 = [sum r_k, sum r_best, lists cut at their best
+    reward, B]}."""
+
+    @staticmethod
+    def forward(ctx, p, labels, spec, r, kind, tau, with_stats=False):
+        if (spec is None) == (r is None) or (spec is None) != (labels is None):
+            raise ValueError("exactly one reward source: labels + spec, or a reward matrix r")
+        B, S = (labels if r is None else r).shape
+        dev = p.device
+        struct = keep = None
+        table = None
+        if spec is not None:
+            struct, keep = spec.native(S, dev)
+            if struct.family == N.REWARD_GAIN and struct.discount is None:
+                table = dcg_table(dev)
+        per_list = _empty((B,), p)
+        loss = _empty((1,), p)
+        dp = _empty((B, S), p)
+        ctx.save_for_backward(dp)
+        ctx.pshape = p.shape
+        k = r_k = r_best = best_k = sums = None
+        if with_stats:
+            k = torch.empty((B,), dtype=torch.int32, device=dev)
+            best_k = torch.empty((B,), dtype=torch.int32, device=dev)
+            r_k, r_best = _empty((B,), p), _empty((B,), p)
+            sums = torch.empty((4,), dtype=torch.float64, device=dev)
+        ws_bytes = query("rlt_reward_any_workspace", B)
+        ws = workspace(ws_bytes, dev)
+        call("rlt_reward_any_loss", ptr(p), ptr(labels), None if struct is None else N.ctypes.byref(struct), ptr(r), B, S, kind, tau,
+             ptr(per_list), ptr(loss), ptr(dp), ptr(k), ptr(r_k), ptr(r_best), ptr(best_k), ptr(sums), ptr(table), ptr(ws), ws_bytes,
+             stream())
+        del keep
+        if not with_stats:
+            return loss.reshape(())
+        ctx.mark_non_differentiable(k, r_k, r_best, best_k, sums)
+        return loss.reshape(()), k, r_k, r_best, best_k, sums
+
+    @staticmethod
+    def backward(ctx, go, *_unused):
+        (dp,) = ctx.saved_tensors
+        g = dp.clone()
+        go = N.f32c(go).reshape(1)
+        call("rlt_scale", ptr(g), ptr(go), g.numel(), stream())
+        return g.view(ctx.pshape), None, None, None, None, None, None
+
+
 class WassDistLossFn(Function):
     """utils/losses.py:236-311: Sinkhorn forward recorded in a workspace, explicit reverse sweep for the gradient."""
 
@@ -1045,6 +1095,42 @@ class MtCutLossFn(Function):
             call("rlt_mt_terms_bwd", ptr(cls), ptr(labels), ptr(terms), B, S, w_r, w_c, ptr(go), ptr(d_rr), ptr(d_cl), stream())
         return (g.view(pshape), None if d_rr is None else d_rr.view(rshape), None if d_cl is None else d_cl.view(cshape),
                 None, None, None, None, None, None, None)
+
+
+class MtSideLossFn(Function):
+    """w_r * rerank hinge + w_c * BCE of MtCutLoss without its cut term (utils/losses.py:180-191): the multi-task pass on its own,
+    for a cut term that another tape node computes (a RewardSpec reward).  rerank or cls may be None."""
+
+    @staticmethod
+    def forward(ctx, rerank, cls, labels, w_r, w_c, margin):
+        B, S = labels.shape
+        dev = labels.device
+        terms = _empty((4,), labels)
+        ws_bytes = query("rlt_mt_terms_workspace", B, S)
+        ws = workspace(ws_bytes, dev)
+        call("rlt_mt_terms", ptr(rerank), ptr(cls), ptr(labels), B, S, margin, ptr(terms), ptr(ws), ws_bytes, stream())
+        xs, ws_ = [], []
+        if rerank is not None:
+            xs.append(terms[0:1]); ws_.append(w_r)
+        if cls is not None:
+            xs.append(terms[1:2]); ws_.append(w_c)
+        loss = _empty((1,), labels)
+        warr = (N.c_float * len(ws_))(*ws_)
+        call("rlt_weighted_sum", N.pointer_array(xs), warr, len(xs), ptr(loss), stream())
+        ctx.save_for_backward(cls, labels, terms)
+        ctx.meta = (w_r, w_c, None if rerank is None else rerank.shape, None if cls is None else cls.shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        cls, labels, terms = ctx.saved_tensors
+        w_r, w_c, rshape, cshape = ctx.meta
+        B, S = labels.shape
+        go = N.f32c(go).reshape(1)
+        d_rr = _empty((B, S), labels) if rshape is not None else None
+        d_cl = _empty((B, S), labels) if cls is not None else None
+        call("rlt_mt_terms_bwd", ptr(cls), ptr(labels), ptr(terms), B, S, w_r, w_c, ptr(go), ptr(d_rr), ptr(d_cl), stream())
+        return (None if d_rr is None else d_rr.view(rshape), None if d_cl is None else d_cl.view(cshape), None, None, None, None)
 
 
 class RerankLossFn(Function):
@@ -1317,6 +1403,18 @@ def reward_matrix(labels, metric, tau=1.0, want_q=False, penalty=-1.0):
     r = _empty((B, S), labels)
     q = _empty((B, S), labels) if want_q else None
     call("rlt_reward_matrix_ex", ptr(labels), ptr(coef), B, S, metric, float(penalty), tau, ptr(r), ptr(q), stream())
+    return (r, q) if want_q else r
+
+
+def reward_spec_matrix(labels, spec, tau=1.0, want_q=False):
+    """The (B,S) fp32 reward of a spec (utils.rewards.RewardSpec) and, with `want_q`, q = softmax(r / tau)."""
+    B, S = labels.shape
+    struct, keep = spec.native(S, labels.device)
+    table = dcg_table(labels.device) if struct.family == N.REWARD_GAIN and struct.discount is None else None
+    r = _empty((B, S), labels)
+    q = _empty((B, S), labels) if want_q else None
+    call("rlt_reward_spec_matrix", ptr(labels), B, S, N.ctypes.byref(struct), float(tau), ptr(table), ptr(r), ptr(q), stream())
+    del keep
     return (r, q) if want_q else r
 
 

@@ -46,6 +46,7 @@ from dataloader import at_dataloader, bicut_dataloader, cp_dataloader, mc_datalo
 from models import AttnCut, BiCut, Choopy, MMOECut, MOECut, MtAttnCut, MtChoopy, PLECut  # noqa: E402
 from utils import losses  # noqa: E402
 from utils.metrics import Metric  # noqa: E402
+from utils.rewards import RewardSpec  # noqa: E402
 from rlt_hip import ops  # noqa: E402
 from rlt_hip.parallel import FORCE_COLLECTIVES, FlatModel, FusedAdam, shard_bounds  # noqa: E402
 
@@ -181,6 +182,14 @@ class Trainer:
         self.history = []                       # per epoch: train / test (loss, f1, dcg) means
         self.baseline_results = None            # --baselines 1: per list length, see baselines()
 
+    @property
+    def reward_stats(self):
+        """A reward loss on a criterion beside f1 / dcg (utils/rewards.py): the epochs also log the reward at the cut, the list's
+        best reward and the share of lists cut at their best reward, from the loss pass itself.  Read off the criterion, so it
+        holds for a Trainer that was given one (verify_probe.py) as for one built from --criterion."""
+        crit = getattr(self, "criterion", None)
+        return hasattr(crit, "forward_with_metrics") and RewardSpec.is_spec(getattr(crit, "metric", None))
+
     # ------------------------------------------------------------------------------------------
     def _step(self, X, y, train):
         """One batch.  Data-parallel: every rank holds the SAME batch (shared permutation) and works on its contiguous
@@ -201,17 +210,32 @@ class Trainer:
                 # AVG all-reduce of sum_r (n_r * world / n) * grad_r / world = sum_r (n_r / n) * grad_r
                 (loss if n_own * self.world == n_all else loss * (n_own * self.world / n_all)).backward()
             stats = torch.stack([loss.detach().double(), f1, dcg, torch.ones((), dtype=torch.float64, device=self.device)]) * n_own
+        if self.reward_stats:                                   # sums over the shard's lists of r_k, r_best and [r_k == r_best]
+            rs = self.criterion.last_reward_sums[:3] if n_own > 0 else torch.zeros(3, dtype=torch.float64, device=self.device)
+            stats = torch.cat([stats, rs])
         if train:
             self.flat.all_reduce_grads()                        # an empty shard contributes its zeroed bucket
             self.optimizer.step()
         if self.world > 1 or (FORCE_COLLECTIVES and dist.is_initialized()):
             dist.all_reduce(stats, op=dist.ReduceOp.SUM)
         vals = stats.tolist()                                   # the step's only host sync
-        return [v / vals[3] for v in vals[:3]]
+        return [v / vals[3] for v in vals[:3]] + [v / vals[3] for v in vals[4:]]
+
+    def _log_reward(self, split, means, epoch):
+        """The reward figures of an epoch under a criterion beside f1 / dcg: mean reward at the cut, mean best reward of the
+        list, share of lists cut at their best reward."""
+        r_k, r_best, share = means
+        self.writer.add_scalar(split + '/reward_at_k_epoch', r_k, epoch)
+        self.writer.add_scalar(split + '/reward_best_epoch', r_best, epoch)
+        self.writer.add_scalar(split + '/cut_at_best_epoch', share, epoch)
+        if self.rank == 0:
+            logging.info('\t{}: reward@k = {:.6f} | best reward = {:.6f} | cut at best = {:.4f}  ({})\n'.format(
+                split.capitalize(), r_k, r_best, share, self.args.criterion))
+        return {"reward_at_k": r_k, "reward_best": r_best, "cut_at_best": share}
 
     def train_epoch(self, epoch):
         start = time.time()
-        tot, step, num_itr = [0.0, 0.0, 0.0], 0, len(self.train_loader)
+        tot, step, num_itr = [0.0] * (6 if self.reward_stats else 3), 0, len(self.train_loader)
         logging.info('-' * 100)
         for X, y in self.train_loader:
             self.model.train()
@@ -220,11 +244,13 @@ class Trainer:
             self.writer.add_scalar('train/loss_step', vals[0], step + num_itr * epoch)   # run.py:146
             tot = [a + b for a, b in zip(tot, vals)]
             step += 1
-        loss, f1, dcg = [v / step for v in tot]                 # unweighted over steps, run.py:153
+        loss, f1, dcg = [v / step for v in tot[:3]]             # unweighted over steps, run.py:153
         self.writer.add_scalar('train/loss_epoch', loss, epoch)
         self.writer.add_scalar('train/F1_epoch', f1, epoch)
         self.writer.add_scalar('train/DCG_epoch', dcg, epoch)
         self.history.append({"epoch": epoch, "train": (loss, f1, dcg)})
+        if self.reward_stats:
+            self.history[-1]["train_reward"] = self._log_reward('train', [v / step for v in tot[3:]], epoch)
         grad = log_grad_guard(self.writer, self.optimizer, epoch)
         if grad is not None:
             self.history[-1]["grad"] = grad
@@ -234,19 +260,23 @@ class Trainer:
         return loss, f1, dcg
 
     def test(self, epoch):
-        tot, step = [0.0, 0.0, 0.0], 0
+        tot, step = [0.0] * (6 if self.reward_stats else 3), 0
         for X, y in self.test_loader:
             self.model.eval()
             with torch.no_grad():
                 vals = self._step(X, y, False)
             tot = [a + b for a, b in zip(tot, vals)]
             step += 1
-        loss, f1, dcg = [v / step for v in tot]                 # run.py:195
+        loss, f1, dcg = [v / step for v in tot[:3]]             # run.py:195
         self.writer.add_scalar('test/loss_epoch', loss, epoch)
         self.writer.add_scalar('test/F1_epoch', f1, epoch)
         self.writer.add_scalar('test/DCG_epoch', dcg, epoch)
         if self.history and self.history[-1]["epoch"] == epoch:
             self.history[-1]["test"] = (loss, f1, dcg)
+        if self.reward_stats:
+            rw = self._log_reward('test', [v / step for v in tot[3:]], epoch)
+            if self.history and self.history[-1]["epoch"] == epoch:
+                self.history[-1]["test_reward"] = rw
         self.f1_record.append(f1)
         self.dcg_record.append(dcg)
         if self.rank == 0:
@@ -344,7 +374,7 @@ class Trainer:
         arrays, summaries, per_len = {}, {}, {}
         qid_all, len_all = [], []
         for L, qids, x, y in self._split_batches(split):
-            rep = CutReport(L, metric=self.args.criterion, device=self.device)
+            rep = CutReport(L, metric=report_metric(self.args.criterion), device=self.device)
             for i in range(0, x.shape[0], self.batch_size):
                 cut = self._forward_eval(x[i:i + self.batch_size])
                 rep.update(cut, y[i:i + self.batch_size] if labelled else None)
@@ -373,7 +403,7 @@ class Trainer:
         fresh = path if path.endswith(".npz") else path + ".npz"
         lines = []
         for other in [o for o in others.split(",") if o]:
-            cmp = compare_reports([other, fresh], metric=self.args.criterion, baseline=0,
+            cmp = compare_reports([other, fresh], metric=report_metric(self.args.criterion), baseline=0,
                                   resamples=10000, seed=self.args.seed or 0, device=self.device)
             lines += cmp.lines()
         for line in lines:
@@ -445,7 +475,7 @@ class Trainer:
             for i in range(0, x.shape[0], self.batch_size):
                 if x[i:i + self.batch_size].shape[0] <= 40:
                     continue
-                rep = CutReport(L, metric=self.args.criterion, tau=0.9, device=self.device)
+                rep = CutReport(L, metric=report_metric(self.args.criterion), tau=0.9, device=self.device)
                 rep.update(self._forward_eval(x[i:i + self.batch_size]), y[i:i + self.batch_size])
                 reward, pred = rep.curves(tail_fix=False)      # the figure's norm_s[-3:] overwrite is presentation: not logged
                 self.writer.add_curve('draw/reward', reward, epoch * 100000 + step)
@@ -512,6 +542,12 @@ def log_grad_guard(writer, optimizer, epoch):
         writer.add_scalar(tag, v, epoch)
     # an epoch without one finite gradient has no mean norm (JSON has no NaN)
     return {tag.split('/', 1)[1]: (v if math.isfinite(v) else None) for tag, v in zip(GRAD_GUARD_TAGS, vals)}
+
+
+def report_metric(criterion):
+    """The metric of the cut report, the comparison and --draw, which know F1 and DCG: the run's criterion, or F1 under a reward
+    beside those two (utils/rewards.py)."""
+    return 'f1' if RewardSpec.is_spec(criterion) else criterion
 
 
 def parse_cut_sweep(spec):

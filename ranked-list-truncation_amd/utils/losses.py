@@ -6,16 +6,44 @@ returns a 0-d tensor supporting .backward() and .item().
 The reference builds its (B,S) reward matrix with B*S python calls of O(S) tensor ops; here the
 reward matrix, its softmax, the divergence and d(loss)/d(output) come out of ONE kernel pass
 (`rlt_reward_loss`), one ranked list per wavefront or per half wavefront.
+
+`metric=` is 'f1' or 'dcg' (that pass, unchanged), or any other cut reward: a utils.rewards.RewardSpec, or a string its
+parse() understands ('fbeta:2', 'ndcg', 'ndcg:-0.5', 'gain:-1,1,3[:norm]'), which goes through `rlt_reward_any_loss`.
+RewardMatrixLoss takes a reward matrix of the caller's instead of labels.
 """
 import torch
 from torch import nn
 
 from rlt_hip import native as N
 from rlt_hip import ops
+from utils.rewards import RewardSpec
 
 
 def _metric_code(metric):
     return N.METRIC_F1 if metric == 'f1' else N.METRIC_DCG      # anything else => DCG (utils/losses.py:218-225)
+
+
+def _spec(metric):
+    """The RewardSpec of a `metric=` argument, None for 'f1' / 'dcg' (and whatever else _metric_code takes as DCG)."""
+    return RewardSpec.parse(metric) if RewardSpec.is_spec(metric) else None
+
+
+def _reward_loss(p, y, metric, kind, tau, with_metrics=False, owner=None):
+    """The criterion on today's F1 / DCG pass, or on rlt_reward_any_loss for any other reward.  with_metrics: (loss, k, sums)
+    with sums = [sum F1@k, sum DCG@k]: from the same pass for 'f1' / 'dcg' (RewardLossFn); for a RewardSpec the pass yields k
+    and the REWARD statistics - left in `owner.last_reward_sums`, (4) float64 = [sum r_k, sum r_best, lists cut at their best
+    reward, B] - and F1@k / DCG@k come from the existing metric call on that k."""
+    spec = _spec(metric)
+    if spec is None:
+        if with_metrics:
+            return ops.RewardLossFn.apply(p, y, _metric_code(metric), kind, tau, -1.0, True)
+        return ops.RewardLossFn.apply(p, y, _metric_code(metric), kind, tau)
+    if not with_metrics:
+        return ops.RewardAnyLossFn.apply(p, y, spec, None, kind, tau)
+    loss, k, _r_k, _r_best, _best_k, rsums = ops.RewardAnyLossFn.apply(p, y, spec, None, kind, tau, True)
+    if owner is not None:
+        owner.last_reward_sums = rsums
+    return loss, k, ops.cut_metrics(p.detach(), y, k_in=k)[3]
 
 
 def _prep(output, labels):
@@ -32,12 +60,12 @@ class ChoopyLoss(nn.Module):
 
     def forward(self, output, labels):
         p, y = _prep(output, labels)
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), N.LOSS_EXPECT, 1.0)
+        return _reward_loss(p, y, self.metric, N.LOSS_EXPECT, 1.0)
 
     def forward_with_metrics(self, output, labels):
         """(loss, k, [sum F1@k, sum DCG@k]) from one kernel pass (utils.metrics.Metric.step)."""
         p, y = _prep(output, labels)
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), N.LOSS_EXPECT, 1.0, -1.0, True)
+        return _reward_loss(p, y, self.metric, N.LOSS_EXPECT, 1.0, True, self)
 
 
 class AttnCutLoss(nn.Module):
@@ -47,11 +75,11 @@ class AttnCutLoss(nn.Module):
 
     def forward(self, output, labels):
         p, y = _prep(output, labels)
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), N.LOSS_CE, float(self.tau))
+        return _reward_loss(p, y, self.metric, N.LOSS_CE, float(self.tau))
 
     def forward_with_metrics(self, output, labels):
         p, y = _prep(output, labels)
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), N.LOSS_CE, float(self.tau), -1.0, True)
+        return _reward_loss(p, y, self.metric, N.LOSS_CE, float(self.tau), True, self)
 
 
 class DivLoss(nn.Module):
@@ -63,12 +91,12 @@ class DivLoss(nn.Module):
     def forward(self, output, labels):
         p, y = _prep(output, labels)
         kind = N.LOSS_KL if self.div_type == 'kl' else N.LOSS_JS
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), kind, float(self.tau))
+        return _reward_loss(p, y, self.metric, kind, float(self.tau))
 
     def forward_with_metrics(self, output, labels):
         p, y = _prep(output, labels)
         kind = N.LOSS_KL if self.div_type == 'kl' else N.LOSS_JS
-        return ops.RewardLossFn.apply(p, y, _metric_code(self.metric), kind, float(self.tau), -1.0, True)
+        return _reward_loss(p, y, self.metric, kind, float(self.tau), True, self)
 
 
 class RerankLoss(nn.Module):
@@ -109,6 +137,13 @@ class MtCutLoss(nn.Module):
         p, y = _prep(y_cut, labels)
         rr = None if y_rerank is None else N.f32c(y_rerank)
         cl = None if y_class is None else N.f32c(y_class)
+        if _spec(self.metric) is not None:
+            # any other reward: the cut term on rlt_reward_any_loss, the rerank hinge and the BCE from the multi-task pass with a
+            # zero cut term of its own, added on the tape in the reference's order (cut + w_r * hinge + w_c * bce)
+            cut = _reward_loss(p, y, self.metric, N.LOSS_JS, float(self.cutloss.tau), with_metrics, self)
+            side = ops.MtSideLossFn.apply(rr, cl, y, float(self.rerank_weight), float(self.classi_weight),
+                                          float(self.rerankloss.margin))
+            return (cut[0] + side,) + tuple(cut[1:]) if with_metrics else cut + side
         return ops.MtCutLossFn.apply(p, rr, cl, y, _metric_code(self.metric), float(self.cutloss.tau),
                                      float(self.rerank_weight), float(self.classi_weight),
                                      float(self.rerankloss.margin), with_metrics)
@@ -118,6 +153,36 @@ class MtCutLoss(nn.Module):
 
     def forward_with_metrics(self, output, labels):
         return self._apply(output, labels, True)
+
+
+class RewardMatrixLoss(nn.Module):
+    """The reward losses on a reward matrix of the caller's: forward(output, r) with r (B,S), r[b,k-1] the value of cutting list b
+    after position k, finite.  kind: 'expect' (ChoopyLoss), 'ce' (AttnCutLoss), 'kl' or 'js' (DivLoss); q = softmax(r / tau).
+    No gradient flows into r."""
+
+    KINDS = {'expect': N.LOSS_EXPECT, 'ce': N.LOSS_CE, 'kl': N.LOSS_KL, 'js': N.LOSS_JS}
+
+    def __init__(self, kind: str = 'js', tau: float = 0.85):
+        super().__init__()
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.KINDS)}, got {kind!r}")
+        if not tau > 0:
+            raise ValueError(f"tau must be positive, got {tau!r}")
+        self.kind, self.tau = kind, float(tau)
+
+    def _apply(self, output, r, with_stats):
+        p, r = _prep(output, r)
+        if r.shape != p.shape[:2]:
+            raise ValueError(f"expected a {tuple(p.shape[:2])} reward matrix, got {tuple(r.shape)}")
+        return ops.RewardAnyLossFn.apply(p, None, None, r.detach(), self.KINDS[self.kind], self.tau, with_stats)
+
+    def forward(self, output, r):
+        return self._apply(output, r, False)
+
+    def forward_with_stats(self, output, r):
+        """(loss, k, stats) as the spec losses' forward_with_metrics."""
+        loss, k, r_k, r_best, best_k, sums = self._apply(output, r, True)
+        return loss, k, {"r_k": r_k, "r_best": r_best, "best_k": best_k, "sums": sums}
 
 
 class BiCutLoss(nn.Module):

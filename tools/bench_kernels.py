@@ -994,6 +994,89 @@ def compare():
         torch.cuda.empty_cache()
 
 
+def reward_any(shapes=((4096, 300), (1048576, 300)), reps=9):
+    """rlt_reward_any_loss (JS, tau 0.85) with the reward built from the labels (F_2) and with a supplied reward matrix, against the
+    torch composition it replaces - float32 softmax of r / tau, logs, the per-list sums, argmax of p and r and the gathers at them, dp
+    by the closed form, on a reward matrix that already exists - and beside rlt_loss_metrics (F1, JS) at the same shape: the pass
+    of equal algorithmic bytes, 12 S per list (8 S read, 4 S of dp written).  HIP events around single alternating launches, the
+    median of `reps`."""
+    from utils.rewards import RewardSpec
+    spec = RewardSpec.fbeta(2.0)
+    tau = 0.85
+    for B, S in shapes:
+        g = torch.Generator(device=dev).manual_seed(11)
+        prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+        y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+        p = torch.softmax(torch.randn(B, S, device=dev, generator=g), 1).contiguous()
+        r = ops.reward_spec_matrix(y, spec)
+        struct, _keep = spec.native(S, dev)
+        tab = ops.dcg_table(dev)
+        per, loss, dp = torch.empty(B, device=dev), torch.empty(1, device=dev), torch.empty(B, S, device=dev)
+        k, bk = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+        rk, rb, sums = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(4, dtype=torch.float64, device=dev)
+        wsb = N.query("rlt_reward_any_workspace", B)
+        ws = N.workspace(wsb, dev)
+        f1, dcg, s2 = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.float64, device=dev), \
+            torch.empty(2, dtype=torch.float64, device=dev)
+        lwsb = N.query("rlt_loss_metrics_workspace", B)
+        lws = N.workspace(lwsb, dev)
+
+        def from_spec():
+            call("rlt_reward_any_loss", ptr(p), ptr(y), N.ctypes.byref(struct), None, B, S, N.LOSS_JS, tau, ptr(per), ptr(loss), ptr(dp),
+                 ptr(k), ptr(rk), ptr(rb), ptr(bk), ptr(sums), None, ptr(ws), wsb, stream())
+
+        def from_matrix():
+            call("rlt_reward_any_loss", ptr(p), None, None, ptr(r), B, S, N.LOSS_JS, tau, ptr(per), ptr(loss), ptr(dp),
+                 ptr(k), ptr(rk), ptr(rb), ptr(bk), ptr(sums), None, ptr(ws), wsb, stream())
+
+        def f1_yardstick():
+            call("rlt_loss_metrics", ptr(p), ptr(y), None, B, S, N.METRIC_F1, -1.0, N.LOSS_JS, tau, -1.0, ptr(per), ptr(loss), ptr(dp),
+                 ptr(k), ptr(f1), ptr(dcg), ptr(s2), ptr(tab), ptr(lws), lwsb, stream())
+
+        def composed_torch():
+            q = torch.softmax(r / tau, 1)
+            lm = torch.log((p + q) * 0.5)
+            lp = torch.log(p)
+            per_t = 0.5 * ((torch.xlogy(q, q) - q * lm).sum(1) + (p * lp - p * lm).sum(1))
+            dp_t = (0.5 / B) * (lp - lm)
+            kk = p.argmax(1, keepdim=True)
+            bb = r.argmax(1, keepdim=True)
+            r_k, r_b = r.gather(1, kk), r.gather(1, bb)
+            return per_t.sum(dtype=torch.float64) / B, dp_t, kk, r_k.sum(dtype=torch.float64), r_b.sum(dtype=torch.float64), (r_k == r_b).sum()
+        fns = (("rlt_reward_any_loss, spec (F_2 from the labels)", from_spec), ("rlt_reward_any_loss, supplied matrix", from_matrix),
+               ("rlt_loss_metrics, F1 (equal bytes)", f1_yardstick), ("torch composition on the matrix", composed_torch))
+        for _name, fn in fns:
+            fn()
+        torch.cuda.synchronize()
+        # the three forms of the new loss agree before anything is timed
+        from_spec()
+        l_spec = loss.clone()
+        from_matrix()
+        ref = composed_torch()
+        assert torch.allclose(l_spec, loss, rtol=1e-6) and abs(float(ref[0]) - float(loss)) <= 1e-4 * abs(float(loss)), (l_spec, loss, ref[0])
+        assert torch.allclose(dp, ref[1], rtol=1e-3, atol=1e-9) and int(ref[5]) == int(sums[2])
+        times = {name: [] for name, _fn in fns}
+        for _ in range(reps):
+            for name, fn in fns:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(b))
+        nbytes = 12.0 * B * S
+        med = {name: sorted(v)[reps // 2] for name, v in times.items()}
+        for name, v in times.items():
+            print(f"reward_any B{B} S{S} {name:48s}: {med[name] * 1e3:10.1f} us (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f}, {reps} calls)  "
+                  f"{nbytes / med[name] / 1e6:8.1f} GB/s on 12 S bytes per list", flush=True)
+        names = [n for n, _ in fns]
+        print(f"reward_any B{B} S{S} spec / rlt_loss_metrics: {med[names[0]] / med[names[2]]:.2f}x   matrix / rlt_loss_metrics: "
+              f"{med[names[1]] / med[names[2]]:.2f}x   torch composition / matrix: {med[names[3]] / med[names[1]]:.2f}x"
+              + ("  (the kernel is SLOWER than the torch composition here)" if med[names[1]] > med[names[3]] else ""), flush=True)
+        del y, p, r, dp, ref
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
