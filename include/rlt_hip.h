@@ -950,6 +950,86 @@ int rlt_grad_norm(const float* g, size_t n, const int64_t* seg_offsets, int n_se
 int rlt_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, rlt_opt_state* state,
                           float lr, float beta1, float beta2, float eps, float weight_decay, int skip_nonfinite, void* stream);
 
+/* ------------------------------------------------------------------ training recipe in one Adam pass (csrc/recipe.hip)
+ * A learning-rate schedule, per-tensor parameter groups (learning-rate factor, weight decay, freezing), coupled or decoupled
+ * (AdamW) weight decay and an exponential moving average of the parameters, in the one streaming pass of the guarded step: no host
+ * read, no allocation, and no scalar the host advances - the schedule is evaluated on the device from the applied-step count of
+ * struct rlt_opt_state, so a skipped step does not advance it.
+ *
+ * struct rlt_recipe: a HOST struct read at call time.  sched_kind: RLT_SCHED_*; weight_decay: the one group's, used when
+ * n_seg == 0; ema_decay 0: no average (ema must then be NULL); skip_nonfinite, use_norm, decoupled, ema_warmup: 0 / 1.
+ * struct rlt_recipe_group: one segment's {lr_scale, weight_decay}; groups = n_seg of them in DEVICE memory, 8-byte aligned, in the
+ * order of seg_offsets - the table of rlt_grad_norm, checked on the host when the host can read it exactly as there.  n_seg == 0
+ * with seg_offsets and groups NULL is one group: lr_scale 1, the recipe's weight_decay.
+ * struct rlt_recipe_state: 32 bytes of DEVICE memory owned by the caller, 8-byte aligned, zero-initialised before the first step
+ * (an int64 view of 4 words reads it; lr, ema_decay, coef are words 4, 5, 6 of its float view):
+ *   lr64, lr       the schedule's float64 value at the last applied step, and that value rounded to float - what the step used
+ *   ema_updates    EMA updates so far;  ema_decay: the decay d of the last one
+ *   coef           scratch of the decision: the clip coefficient the update applies
+ * The decision's other scratch is apply, bc1, bc2_sqrt of struct rlt_opt_state, as in the guarded step.
+ *
+ * The decision (one lane).  use_norm != 0: coef and nonfinite come from `state`, so a rlt_grad_norm call precedes on the same
+ * stream; otherwise coef = 1 and nothing is skipped.  use_norm, skip_nonfinite and nonfinite != 0: the step is skipped - no byte of
+ * p, m, v, ema or the recipe state changes, `step` stays, skipped += 1.  Otherwise t = ++step, clipped += 1 when coef < 1, the bias
+ * corrections as in the guarded step (float64 pow, once), and the schedule in float64, each expression evaluated left to right as
+ * written with every integer converted to float64 first, B = (double)base_lr, F = B * (double)min_lr_ratio, W = warmup_steps,
+ * T = total_steps:
+ *   t <= W                 B * t / W
+ *   W < t <= T  CONSTANT   B
+ *               LINEAR     F + (B - F) * (T - t) / (T - W)
+ *               COSINE     F + (B - F) * 0.5 * (1.0 + cos(pi * (t - W) / (T - W)))          pi = 3.14159265358979323846
+ *   t > T                  F (B for CONSTANT, which never reads T)
+ * rounded to float once.  With ema: d = ema_decay, or with ema_warmup min((double)ema_decay, (1.0 + k) / (10.0 + k)) rounded to
+ * float, k = the EMA updates before this one.  rlt_lr_at evaluates the same expression on the host (no device needed; t >= 1; NaN
+ * for a recipe the step would refuse): equal bit for bit to the device's for CONSTANT and LINEAR, up to the two cos for COSINE.
+ *
+ * The update, per element of segment s, lr_s = lr * lr_scale[s] and wd_s = weight_decay[s] in float, gr and the moments as in the
+ * guarded step (m = b1 m + (1 - b1) gr, v = b2 v + (1 - b2) gr gr, denom = sqrt(v) / bc2_sqrt + eps, u = (lr_s / bc1) * (m / denom)):
+ *   coupled     gr = g * coef + wd_s * p (the term is left out when wd_s == 0),   p = p - u
+ *   decoupled   gr = g * coef,   p = p - (lr_s * wd_s * p + u): torch.optim.AdamW's p * (1 - lr_s wd_s) - u with the decay taken
+ *               from the parameter before the update, written so that p is rounded once at its own magnitude
+ *   ema         ema = d * ema + (1 - d) * p with the new p; the caller initialises ema to a copy of p
+ *   lr_scale[s] == 0 freezes the segment: none of its bytes in p, m, v, ema is read or written.
+ * g is not modified.  The bucket is cut into chunks of RLT_RECIPE_CHUNK elements at absolute positions, one per workgroup and trip
+ * of a grid of min(chunks, RLT_RECIPE_GRID) workgroups (the two query functions return the constants); a chunk's first segment is
+ * found by one search of the table, the boundaries inside it by walking forward: no per-element side array.  Two launches.
+ * Algorithmic bytes: 20n read, 16n written with ema; 16n read, 12n written without (+ the table: 16 n_seg bytes).
+ * Errors before any launch: RLT_E_ARG (p, g, m, v, state, rstate or recipe NULL; n == 0; n_seg < 0; n_seg > 0 without both tables
+ * or n_seg == 0 with one; a NaN in the recipe; sched_kind outside its codes; warmup_steps < 0; LINEAR or COSINE with
+ * total_steps <= warmup_steps; min_lr_ratio outside [0, 1]; ema_decay outside [0, 1); ema without ema_decay or ema_decay without
+ * ema; a host-readable segment table that is not as rlt_grad_norm wants it), RLT_E_SHAPE (n % 4, n > 2^46), RLT_E_ALIGN (p, g, m, v,
+ * ema off 16 bytes; state, rstate, seg_offsets, groups off 8).
+ *
+ * rlt_swap_f32 exchanges two fp32 buffers in place (n % 4 == 0, 16-byte aligned, not overlapping: RLT_E_SHAPE / RLT_E_ALIGN /
+ * RLT_E_ARG): evaluating with the averaged weights costs no second bucket.  Algorithmic bytes: 8n read, 8n written. */
+#define RLT_SCHED_CONSTANT 0
+#define RLT_SCHED_LINEAR   1
+#define RLT_SCHED_COSINE   2
+#define RLT_RECIPE_CHUNK 4096
+#define RLT_RECIPE_GRID  2048
+typedef struct rlt_recipe {
+    float base_lr, beta1, beta2, eps, weight_decay;
+    int32_t decoupled;
+    int32_t sched_kind;
+    int32_t ema_warmup;
+    int64_t warmup_steps, total_steps;
+    float min_lr_ratio, ema_decay;
+    int32_t skip_nonfinite, use_norm;
+} rlt_recipe;
+typedef struct rlt_recipe_group { float lr_scale, weight_decay; } rlt_recipe_group;
+typedef struct rlt_recipe_state {
+    double lr64;
+    int64_t ema_updates;
+    float lr, ema_decay, coef, reserved;
+} rlt_recipe_state;
+size_t rlt_recipe_chunk(void);
+int rlt_recipe_grid(void);
+double rlt_lr_at(const rlt_recipe* recipe, int64_t t);
+int rlt_adam_step_recipe(float* p, const float* g, float* m, float* v, float* ema, size_t n, const int64_t* seg_offsets,
+                         const rlt_recipe_group* groups, int n_seg, rlt_opt_state* state, rlt_recipe_state* rstate,
+                         const rlt_recipe* recipe, void* stream);
+int rlt_swap_f32(float* a, float* b, size_t n, void* stream);
+
 /* ------------------------------------------------------------------ paired significance tests (csrc/compare.hip)
  * Is system m better than the baseline on the same queries?  base (Q) and sys (M rows of Q, leading dimension ld >= Q) are float32
  * per-query values in one query order (columns of run.py --report-out).  One call leaves, per system, a record of

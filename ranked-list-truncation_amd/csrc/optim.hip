@@ -19,6 +19,7 @@
 // the segment starts off a chunk edge) and the head records of the chunks that start inside it, in ascending order, summed lane
 // by lane (item i in lane i % 64) and by the DPP scan; the bucket's figures are the segment figures summed the same way.
 #include "common.h"
+#include "seg_table.h"
 
 namespace {
 
@@ -64,16 +65,6 @@ __device__ __forceinline__ Fig fig_wave(const Fig& f) {
     r.nan = wave_sum(f.nan);
     r.max_abs = rlt_readlane(wave_scan_op(f.max_abs, 0.0, [](double a, double b) { return fmax(a, b); }), 63);
     return r;
-}
-
-// largest s in [0, n_seg) with off[s] <= pos (0 when there is none): the segment that holds element pos of an ascending table
-__device__ __forceinline__ int seg_of(const long long* __restrict__ off, int n_seg, long long pos) {
-    int lo = 0, hi = n_seg;                       // invariant: the answer is in [lo, hi)
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (off[mid] <= pos) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // ---------------------------------------------------------------- the pass: one record per chunk (+ one per segment start)
@@ -258,18 +249,6 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p
 inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 inline long long chunks_of(size_t n) { return (long long)((n + CHUNK - 1) / CHUNK); }
 
-// A segment table the HOST can read (pinned or managed memory, or a process without a device) is checked before the launch; one
-// in device memory cannot be read without a synchronising copy and is the caller's duty (the kernels stay in bounds with any
-// table).  1: host-readable.
-bool host_readable(const void* ptr) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) {
-        (void)hipGetLastError();                  // not known to the runtime, or no device: plain host memory
-        return true;
-    }
-    return a.type != hipMemoryTypeDevice;
-}
-
 }  // namespace
 
 extern "C" {
@@ -290,11 +269,7 @@ int rlt_grad_norm(const float* g, size_t n, const int64_t* seg_offsets, int n_se
     RLT_CHECK_SHAPE(n % 4 == 0 && n <= ((size_t)1 << 46));
     if (!rlt_aligned16(g) || ((uintptr_t)seg_offsets & 7u) || ((uintptr_t)seg_out & 7u) || ((uintptr_t)state & 7u)) return RLT_E_ALIGN;
     if (!rlt_aligned16(ws) || ws_bytes < rlt_grad_norm_workspace(n, n_seg)) return RLT_E_WORKSPACE;
-    if (n_seg > 0 && host_readable(seg_offsets)) {
-        if (seg_offsets[0] != 0 || seg_offsets[n_seg] != (int64_t)n) return RLT_E_ARG;
-        for (int s = 0; s < n_seg; ++s)
-            if (seg_offsets[s + 1] < seg_offsets[s] || seg_offsets[s] % 4 != 0) return RLT_E_ARG;
-    }
+    if (n_seg > 0 && host_readable(seg_offsets) && !seg_table_ok(seg_offsets, n_seg, n)) return RLT_E_ARG;
     const long long nc = chunks_of(n);
     const int ns = n_seg > 0 ? n_seg : 1;
     Fig* head = (Fig*)ws;

@@ -6,7 +6,7 @@ a raw device pointer.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_uint32, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 import torch
 
@@ -122,6 +122,12 @@ _SIGNATURES = {
     "rlt_grad_norm_workspace": (c_size_t, [c_size_t, c_int]),
     "rlt_grad_norm": (c_int, [P, c_size_t, P, c_int, c_float, P, c_size_t, P, P, P]),
     "rlt_adam_step_guarded": (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    # training recipe in one Adam pass: schedule, parameter groups, AdamW, EMA (csrc/recipe.hip)
+    "rlt_recipe_chunk": (c_size_t, []),
+    "rlt_recipe_grid": (c_int, []),
+    "rlt_lr_at": (c_double, [P, c_int64]),
+    "rlt_adam_step_recipe": (c_int, [P, P, P, P, P, c_size_t, P, P, c_int, P, P, P, P]),
+    "rlt_swap_f32": (c_int, [P, P, c_size_t, P]),
     # paired significance tests between per-query columns (csrc/compare.hip)
     "rlt_paired_compare_plan": (c_int, [c_int, c_int, c_int, P]),
     "rlt_paired_compare_workspace": (c_size_t, [c_int, c_int, c_int]),
@@ -268,6 +274,35 @@ OPT_STEP, OPT_SKIPPED, OPT_CLIPPED, OPT_NONFINITE, OPT_NAN = 0, 1, 2, 3, 4
 OPT_SUMSQ, OPT_NORM, OPT_MAX_ABS, OPT_NORM_SUM, OPT_NORM_MAX, OPT_NORM_STEPS = 5, 6, 7, 8, 9, 10
 OPT_COEF_F32 = 22                                  # index of `coef` in the float32 view
 GRAD_SEG_WORDS = 3                                 # rlt_grad_seg: sumsq (float64), nonfinite (int64), max_abs (float64)
+
+
+# rlt_recipe_state as 4 int64 words: lr64 (float64 view) and ema_updates, then lr, ema_decay, coef through .view(torch.float32)
+RECIPE_STATE_WORDS = 4
+RECIPE_LR64, RECIPE_EMA_UPDATES = 0, 1
+RECIPE_LR_F32, RECIPE_EMA_DECAY_F32, RECIPE_COEF_F32 = 4, 5, 6
+SCHED_KINDS = ("constant", "linear", "cosine")                                      # RLT_SCHED_CONSTANT .. RLT_SCHED_COSINE
+RECIPE_FIELDS = (("base_lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
+                 ("decoupled", c_int32), ("sched_kind", c_int32), ("ema_warmup", c_int32), ("warmup_steps", c_int64),
+                 ("total_steps", c_int64), ("min_lr_ratio", c_float), ("ema_decay", c_float), ("skip_nonfinite", c_int32),
+                 ("use_norm", c_int32))
+
+
+class RecipeStruct(ctypes.Structure):
+    """rlt_recipe of include/rlt_hip.h: a host struct, read by the library at call time."""
+    _fields_ = list(RECIPE_FIELDS)
+
+
+def recipe_struct(base_lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False, sched_kind="constant",
+                  warmup_steps=0, total_steps=0, min_lr_ratio=0.0, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False, use_norm=False):
+    """-> RecipeStruct; sched_kind by its name in SCHED_KINDS or by its code."""
+    kind = SCHED_KINDS.index(sched_kind) if sched_kind in SCHED_KINDS else int(sched_kind)
+    return RecipeStruct(base_lr, beta1, beta2, eps, weight_decay, int(bool(decoupled)), kind, int(bool(ema_warmup)), int(warmup_steps),
+                        int(total_steps), min_lr_ratio, ema_decay or 0.0, int(bool(skip_nonfinite)), int(bool(use_norm)))
+
+
+def lr_at(recipe, t):
+    """rlt_lr_at: the schedule's float64 value at applied step t >= 1, on the host (NaN for a recipe the step would refuse)."""
+    return float(load().rlt_lr_at(ctypes.byref(recipe), int(t)))
 
 
 # the record of rlt_paired_compare: CMP_WORDS 8-byte words per system (RLT_CMP_*), the float64 ones through .view(torch.float64)

@@ -30,6 +30,7 @@ state_dict checkpoint on best test F1, run.py:153-232) and the same log lines.  
 """
 import argparse
 import configparser
+import contextlib
 import json
 import logging
 import math
@@ -49,6 +50,7 @@ from utils.metrics import Metric  # noqa: E402
 from utils.rewards import RewardSpec  # noqa: E402
 from rlt_hip import ops  # noqa: E402
 from rlt_hip.parallel import FORCE_COLLECTIVES, FlatModel, FusedAdam, shard_bounds  # noqa: E402
+from utils.recipe import add_recipe_arguments, recipe_kwargs  # noqa: E402
 
 
 class ScalarLog:
@@ -105,6 +107,11 @@ class Trainer:
         # on cuda:0 over gloo, as bench.py's RLT_BENCH_DEVICE does); real runs use one GPU per rank over RCCL
         self.device = torch.device("cuda", int(os.environ.get("RLT_RUN_DEVICE", os.environ.get("LOCAL_RANK", "0"))))
         torch.cuda.set_device(self.device)
+        # --resume: the checkpoint of --save-state.  The data permutation and the dropout streams are not part of it: they restart
+        # from --seed + the resumed epoch, so a resumed run is not bit-identical to an uninterrupted one (the optimizer is)
+        resume = torch.load(args.resume, map_location="cpu") if getattr(args, "resume", None) else None
+        self.start_epoch = resume["epoch"] + 1 if resume else 0
+        seed = args.seed + self.start_epoch if resume and args.seed is not None else args.seed
 
         name = self.model_name
         if name in ('choopy', 'mtchoopy'):
@@ -122,11 +129,11 @@ class Trainer:
         with rank_data.labels_optional(not need_labels):
             if self.sparse_bicut:
                 self.train_loader, self.test_loader, data = bicut_dataloader(
-                    args.retrieve_data, args.dataset_name, args.batch_size, device=self.device, base=args.dataset_base, seed=args.seed,
+                    args.retrieve_data, args.dataset_name, args.batch_size, device=self.device, base=args.dataset_base, seed=seed,
                     stats=args.bicut_stats, vocab=args.bicut_vocab)
             else:
                 self.train_loader, self.test_loader, data = loader(args.retrieve_data, args.dataset_name, args.batch_size,
-                                                                   device=self.device, base=args.dataset_base, seed=args.seed)
+                                                                   device=self.device, base=args.dataset_base, seed=seed)
         # the reference hard-codes 3 / 25 / 47 input features and 300 / 40 positions (run.py:34,60,70,86); here both
         # come from the files, and a mismatch with the reference's numbers is reported instead of mis-striding the LSTM
         self.data = data
@@ -176,10 +183,22 @@ class Trainer:
             self.load_model()
         self.flat = FlatModel(self.model)
         self.flat.broadcast_params()
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **grad_guard_kwargs(args))   # run.py:104
+        if resume:
+            self.model.load_state_dict(resume["model"])         # in place: into the views of the flat bucket
+        total_steps = max(1, args.epochs * len(self.train_loader))
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **grad_guard_kwargs(args),   # run.py:104
+                                   **recipe_kwargs(args, self.flat.names, total_steps))
+        self.ema_eval = bool(getattr(args, "ema_eval", 0))      # (drivers build their own Namespace)
+        if resume:
+            self.optimizer.load_state_dict(resume["optimizer"])
+            for k in ("best_test_f1", "best_test_dcg", "best_epoch", "f1_record", "dcg_record", "history"):
+                setattr(self, k, resume[k])
+            if args.seed is not None:
+                torch.manual_seed(seed)
         ops.set_seed_stream(self.rank)          # same torch seed on every rank, different dropout masks
         self.writer = ScalarLog(getattr(args, "tensorboard_dir", None) if self.rank == 0 else None)   # run.py:111
-        self.history = []                       # per epoch: train / test (loss, f1, dcg) means
+        if not resume:
+            self.history = []                   # per epoch: train / test (loss, f1, dcg) means
         self.baseline_results = None            # --baselines 1: per list length, see baselines()
 
     @property
@@ -254,12 +273,24 @@ class Trainer:
         grad = log_grad_guard(self.writer, self.optimizer, epoch)
         if grad is not None:
             self.history[-1]["grad"] = grad
+        if self.optimizer.recipe:                               # the learning rate of the epoch's last applied step
+            lr = self.optimizer.epoch_stats(reset=False)["lr"]
+            self.writer.add_scalar('train/lr', lr, epoch)
+            self.history[-1]["lr"] = lr
         if self.rank == 0:
             logging.info('\nEpoch: {} | Epoch Time: {:.2f} s'.format(epoch, time.time() - start))
             logging.info('\tTrain: loss = {} | f1 = {:.6f} | dcg = {:.6f}\n'.format(loss, f1, dcg))
         return loss, f1, dcg
 
+    def eval_weights(self):
+        """--ema-eval 1: the block computes with the averaged weights (FusedAdam.ema_weights); otherwise with the raw iterate."""
+        return self.optimizer.ema_weights() if getattr(self, "ema_eval", False) else contextlib.nullcontext()
+
     def test(self, epoch):
+        with self.eval_weights():
+            return self._test(epoch)
+
+    def _test(self, epoch):
         tot, step = [0.0] * (6 if self.reward_stats else 3), 0
         for X, y in self.test_loader:
             self.model.eval()
@@ -295,6 +326,16 @@ class Trainer:
         state = {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}
         torch.save(state, os.path.join(self.save_path, '{}.pkl'.format(self.model_name)))
         logging.info('The best model has beed updated and saved in {}\n'.format(self.save_path))
+
+    def save_state(self, path, epoch):
+        """--save-state: the training checkpoint after `epoch` - model, optimizer state_dict (moments, step count, ema, recipe
+        state), the epoch, the best figures and the records.  --resume continues from it."""
+        opt = {k: (v.detach().clone().cpu() if torch.is_tensor(v) else v) for k, v in self.optimizer.state_dict().items()}
+        state = {"model": {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}, "optimizer": opt, "epoch": epoch,
+                 "best_test_f1": self.best_test_f1, "best_test_dcg": self.best_test_dcg, "best_epoch": self.best_epoch,
+                 "f1_record": self.f1_record, "dcg_record": self.dcg_record, "history": self.history}
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save(state, path)
 
     def load_model(self):
         self.model.load_state_dict(torch.load(self.model_path, map_location=self.device))
@@ -487,18 +528,21 @@ class Trainer:
             self.baseline_results = self.baselines()
         if self.rank == 0:
             logging.info('\nTrain the {} model: \n'.format(self.model_name))
-        for epoch in range(self.epochs):
+        for epoch in range(getattr(self, "start_epoch", 0), self.epochs):
             self.train_epoch(epoch)
             self.test(epoch)
             if getattr(self.args, "draw", 0) and epoch % 2 == 0 and self.rank == 0:      # (drivers build their own Namespace)
                 self.draw(epoch)
-        if getattr(self.args, "report_out", None) and self.rank == 0:
-            self.report_results = self.report(self.args.report_out, getattr(self.args, "report_split", "test"),
-                                              bool(getattr(self.args, "report_labels", 1)))
-            if getattr(self.args, "compare_to", None):
-                self.compare_lines = self.compare(self.args.report_out, self.args.compare_to)
-        if getattr(self.args, "cut_sweep", None) and self.rank == 0:
-            self.sweep_results = self.cut_sweep(self.args.cut_sweep, getattr(self.args, "sweep_out", None))
+            if getattr(self.args, "save_state", None) and self.rank == 0:
+                self.save_state(self.args.save_state, epoch)
+        with self.eval_weights():
+            if getattr(self.args, "report_out", None) and self.rank == 0:
+                self.report_results = self.report(self.args.report_out, getattr(self.args, "report_split", "test"),
+                                                  bool(getattr(self.args, "report_labels", 1)))
+                if getattr(self.args, "compare_to", None):
+                    self.compare_lines = self.compare(self.args.report_out, self.args.compare_to)
+            if getattr(self.args, "cut_sweep", None) and self.rank == 0:
+                self.sweep_results = self.cut_sweep(self.args.cut_sweep, getattr(self.args, "sweep_out", None))
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -619,6 +663,14 @@ def build_parser():
     p.add_argument('--bicut-vocab', type=int, default=None,
                    help="dictionary size V of --bicut-stats (the reference: 231448); default 1 + the largest term id of the file")
     add_grad_guard_arguments(p)
+    add_recipe_arguments(p)
+    p.add_argument('--save-state', type=str, default=None,
+                   help="rank 0 writes a training checkpoint here after every epoch: model, optimizer state (moments, step count, "
+                        "averaged weights, schedule state), epoch, best figures and records")
+    p.add_argument('--resume', type=str, default=None,
+                   help="continue from a --save-state checkpoint at the epoch after it.  The data permutation and the dropout streams "
+                        "are not restored - they restart from --seed + that epoch - so the run is not bit-identical to an "
+                        "uninterrupted one; the optimizer state is")
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Truncation'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

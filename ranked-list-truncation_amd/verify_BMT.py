@@ -75,7 +75,8 @@ class Trainer:
         E = width if self.ft else feat
         self.model = (TaskC if self.verify_type == 'c' else TaskR)(d_model=E).to(self.device)
         self.flat = FlatModel(self.model)
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args),
+                                   **run.recipe_kwargs(args, self.flat.names, max(1, args.epochs * len(self.train_loader))))
         self.writer = run.ScalarLog(args.tensorboard_dir)
 
     def features(self, X):
@@ -172,6 +173,7 @@ def build_parser():
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--history-json', type=str, default=None, help="per-epoch train / test means and the train metric list")
     run.add_grad_guard_arguments(p)
+    run.add_recipe_arguments(p, ema_eval=False)
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Verify'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

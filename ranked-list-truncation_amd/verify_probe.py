@@ -67,7 +67,8 @@ def base_trainer(args, model, loaders, device):
     t.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
     t.multi_task = True
     t.flat = FlatModel(model)
-    t.optimizer = FusedAdam(t.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
+    t.optimizer = FusedAdam(t.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args),
+                            **run.recipe_kwargs(args, t.flat.names, max(1, args.epochs_base * len(t.train_loader))))
     t.writer = run.ScalarLog(os.path.join(args.tensorboard_dir, 'base') if args.tensorboard_dir else None)
     return t
 
@@ -91,7 +92,8 @@ class Trainer:
                                         dropout=args.dropout, num_experts=2).to(self.device)
         self.probe = Probe().to(self.device)
         self.flat = FlatModel(self.probe)
-        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args))
+        self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **run.grad_guard_kwargs(args),
+                                   **run.recipe_kwargs(args, self.flat.names, max(1, args.epochs_probe * len(self.train_loader))))
         self.writer = run.ScalarLog(args.tensorboard_dir)
         self.base_history, self.history = None, []
         self.step = 0
@@ -176,6 +178,7 @@ def build_parser():
     p.add_argument('--seed', type=int, default=None)
     p.add_argument('--history-json', type=str, default=None, help="the base's per-epoch history and the probes' epoch means")
     run.add_grad_guard_arguments(p)
+    run.add_recipe_arguments(p, ema_eval=False)
     p.add_argument('--tensorboard-dir', type=str, default=os.path.join(HERE, 'Tensorboard_summary', 'Probe'),
                    help="scalars.jsonl (+ tensorboard event files when tensorboard is installed); '' disables")
     return p

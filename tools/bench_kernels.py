@@ -858,6 +858,86 @@ def optim(reps=15):
         torch.cuda.empty_cache()
 
 
+def recipe(reps=9):
+    """The recipe step (csrc/recipe.hip) at AttnCut's 1,846,785 parameters (padded as FlatModel pads its slots) and at BiCut's
+    237.6 M.  (a) rlt_adam_step_guarded alone against the recipe step without EMA and with one group: equal bytes, 28 n.  (b) the
+    recipe step with EMA and AttnCut's real group table (no decay on biases and norms, the cut head at half the rate; at BiCut's
+    size the same 30 slots scaled up) against the composition it replaces: rlt_adam_step_guarded + ema.lerp_(p, 1 - d) + a
+    host-computed lr - the common, non-skipped step.  HIP events around single alternating launches, the median of `reps`; GB/s on
+    each pass's algorithmic bytes (recipe with EMA 36 n, the composition 40 n)."""
+    import ctypes
+    import math
+    import models
+    from rlt_hip.parallel import FlatModel, resolve_param_groups
+    lr, b1, b2, eps, wd, d = 3e-5, 0.9, 0.999, 1e-8, 0.005, 0.999
+    flat = FlatModel(models.AttnCut(input_size=3))
+    groups = resolve_param_groups(flat.names, [("*bias*", {"weight_decay": 0.0}), ("*norm*", {"weight_decay": 0.0}),
+                                               ("decison_layer.*", {"lr_scale": 0.5})], wd)
+    sizes = [int(b - a) for a, b in zip(flat.offsets.tolist(), flat.offsets.tolist()[1:])]
+    for label, n in (("AttnCut", flat.numel), ("BiCut", 237600000)):
+        k = n // flat.numel                                      # BiCut's size: the same table with every slot k times as long
+        offs = [0]
+        for sz in sizes:
+            offs.append(offs[-1] + sz * k)
+        offs[-1] = n
+        off_t = torch.tensor(offs, dtype=torch.int64, device=dev)
+        grp_t = torch.tensor(groups, dtype=torch.float32, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(3)
+        p, g = torch.randn(n, device=dev, generator=gen), torch.randn(n, device=dev, generator=gen) * 1e-3
+        m, v, ema = torch.zeros(n, device=dev), torch.zeros(n, device=dev), p.clone()
+        state = torch.zeros(N.OPT_STATE_WORDS, dtype=torch.int64, device=dev)
+        rstate = torch.zeros(N.RECIPE_STATE_WORDS, dtype=torch.int64, device=dev)
+        sched = dict(sched_kind="cosine", warmup_steps=100, total_steps=100000, min_lr_ratio=0.1)
+        r_plain = N.recipe_struct(base_lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, **sched)
+        r_full = N.recipe_struct(base_lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, decoupled=True, ema_decay=d, **sched)
+        t = [0]
+
+        def guarded():
+            call("rlt_adam_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(state), lr, b1, b2, eps, wd, 0, stream())
+
+        def recipe_plain():
+            call("rlt_adam_step_recipe", ptr(p), ptr(g), ptr(m), ptr(v), None, n, None, None, 0, ptr(state), ptr(rstate),
+                 ctypes.byref(r_plain), stream())
+
+        def recipe_full():
+            call("rlt_adam_step_recipe", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), n, ptr(off_t), ptr(grp_t), len(groups), ptr(state),
+                 ptr(rstate), ctypes.byref(r_full), stream())
+
+        def composed():
+            t[0] += 1
+            lr_t = lr * 0.5 * (1.0 + math.cos(math.pi * min(t[0], 100000) / 100000))       # the host advances the schedule
+            call("rlt_adam_step_guarded", ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(state), lr_t, b1, b2, eps, wd, 0, stream())
+            ema.lerp_(p, 1.0 - d)
+        fns = (("adam_step_guarded", guarded, 28), ("recipe, no ema, 1 group", recipe_plain, 28), ("recipe, ema, 30 groups", recipe_full, 36),
+               ("guarded + lerp_ + host lr", composed, 40))
+        times = {name: [] for name, _, _ in fns}
+        call("rlt_grad_norm", ptr(g), n, None, 0, 0.0, ptr(N.byte_buffer(N.query("rlt_grad_norm_workspace", n, 0), dev)),
+             N.query("rlt_grad_norm_workspace", n, 0), None, ptr(state), stream())          # coef = 1, nonfinite = 0 in the state
+        for _ in range(2):
+            for _, fn, _ in fns:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for name, fn, _ in fns:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(b))
+        med = {name: sorted(ts)[reps // 2] for name, ts in times.items()}
+        for name, _, per in fns:
+            ms, ts = med[name], times[name]
+            print(f"recipe {label:8s} n={n:10d} {name:26s}: {ms * 1e3:9.1f} us (min {min(ts) * 1e3:.1f}, max {max(ts) * 1e3:.1f})  "
+                  f"{per * n / ms / 1e6:8.1f} GB/s on {per} n bytes = {per * n / ms / 1e6 / 8000 * 100:4.1f} % of 8 TB/s", flush=True)
+        names = [nm for nm, _, _ in fns]
+        print(f"recipe {label:8s} recipe (no ema) / guarded: {med[names[1]] / med[names[0]]:.2f}x;  composition / recipe (ema, groups): "
+              f"{med[names[3]] / med[names[2]]:.2f}x"
+              + ("  (the fused pass is SLOWER than the composition here)" if med[names[2]] > med[names[3]] else ""), flush=True)
+        del p, g, m, v, ema
+        torch.cuda.empty_cache()
+
+
 def compare():
     """The paired comparison pass (rlt_paired_compare: R sign-flip replicates and R bootstrap replicates of M systems over Q
     queries) against the best torch composition of the same two statistics, tiled over replicates so that its tensors fit.
