@@ -190,6 +190,44 @@ int rlt_reward_any_loss(const float* p, const float* labels, const rlt_reward_sp
                         int32_t* k_out, float* r_k, float* r_best, int32_t* best_k, double* sums,
                         const void* dcg_table, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ evaluation in any cut reward (csrc/reward_eval.hip)
+ * What the truncation baselines, the cut report, the cut sweep and the paired comparison need from a reward row, in one pass.
+ * The reward: exactly one source, as for rlt_reward_any_loss - labels + spec, or r_in (B,S) fp32 (labels and spec NULL).
+ *   r[b,k], k = 1..S, is bit for bit the fp32 value rlt_reward_spec_matrix writes for the same labels and spec (one device
+ *   text builds both: csrc/reward_form.h), or r_in itself; r[b,0] = 0: cutting before the first document keeps nothing, the
+ *   k = 0 entry of rlt_truncation_curves.
+ * Cuts: k_in (B,T) int32, row-major, 0 <= T <= 64; T = 0 (k_in is then not read) means no cuts.  The T columns are the cuts of
+ *   T rules or systems on the same lists: the (B,T) output of rlt_cut_sweep, or the k of rlt_cut_report.  A cut outside 0..S is
+ *   clamped into that range and counted.
+ * Per-list outputs (each may be NULL):
+ *   r_at (B,T) fp32 = r[b, k_in[b,t]];
+ *   better (B,T) int32 = the number of cuts k in kmin..S with r[b,k] strictly greater than r_at[b,t]; kmin = 0 with allow_empty,
+ *   otherwise 1;
+ *   best (B) fp32 and best_k (B) int32 = the row's largest reward over kmin..S and its first position: np.argmax on the
+ *   (S+1)-entry row, so k = 0 wins a tie with allow_empty.
+ * Split outputs (float64, 8-byte aligned, each may be NULL; accumulate = 1 ADDS this batch, 0 overwrites):
+ *   curve (S+1) = sum over lists of r[b,k], k = 0..S (entry 0 is 0): Fixed-k at every k at once, and Greedy-k;
+ *   best_hist (S+1) = counts of best_k;
+ *   sums (3 + 3T): [0] the number of lists, [1] sum best, [2] the number of clamped cuts, then per t: sum r_at,
+ *   #(r_at == best), sum better.
+ * dcg_table: as for rlt_reward_any_loss.  ws: rlt_reward_eval_workspace(B, S, T) bytes, 8-byte aligned (0 for B <= 0, S outside
+ * 1..1024 or T outside 0..64; never smaller for a larger B).
+ * Layout as rlt_reward_any_loss: a wavefront owns whole lists, four, two or one by S and S % 4; rows of S % 4 == 0 floats are
+ * read 16 bytes at a time, so labels and r_in must then be 16-byte aligned.  The reward row stays in registers, the sums per
+ * position are kept per lane, the cuts are served from a copy of the row in LDS.  Two launches (one without split outputs): the
+ * pass (every workgroup leaves one float64 record in ws) and a fixed-order column reduction.  No atomics, no allocation, no host
+ * synchronisation: two calls give the same bits.  Errors before any launch, in this order: RLT_E_ARG (both or neither reward
+ * source; non-positive B or S; T outside 0..64; T > 0 with k_in NULL; r_at or better with T = 0; every output NULL; a spec
+ * outside its ranges, a GAIN spec with neither discount nor dcg_table; ws NULL), RLT_E_SHAPE (S > 1024), RLT_E_ALIGN (rows; 8
+ * bytes for curve, best_hist, sums, ws and the table; 4 for the rest), RLT_E_WORKSPACE.
+ * Algorithmic bytes per list: read 4 S + 4 T, write up to 8 T + 8. */
+size_t rlt_reward_eval_workspace(int B, int S, int T);
+int rlt_reward_eval(const float* labels, const rlt_reward_spec* spec, const float* r_in, int B, int S,
+                    const int32_t* k_in, int T, int allow_empty, const void* dcg_table, int accumulate,
+                    float* r_at, int32_t* better, float* best, int32_t* best_k,
+                    double* curve, double* best_hist, double* sums,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ multi-task terms (L7-L8)
  * utils/losses.py:99-141 (RerankLoss) and nn.BCELoss of :177,:187 (MtCutLoss).
  * rlt_mt_terms: one pass over the rerank scores and/or class probabilities (either may be NULL)

@@ -11,7 +11,8 @@ from utils.compare import compare_reports, is_best_cut, write_json
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("reports", nargs="+", help=".npz files written by run.py --report-out")
-    p.add_argument("--metric", choices=("f1", "dcg"), default="f1")
+    p.add_argument("--metric", choices=("f1", "dcg", "reward"), default="f1",
+                   help="reward: the columns of a report written with run.py --eval-reward (the files must share one reward)")
     p.add_argument("--baseline", default="0", help="index of the baseline file, or Oracle")
     p.add_argument("--resamples", type=int, default=10000)
     p.add_argument("--seed", type=int, default=0)

@@ -45,6 +45,9 @@ _SIGNATURES = {
     "rlt_reward_spec_matrix": (c_int, [P, c_int, c_int, P, c_float, P, P, P, P]),
     "rlt_reward_any_workspace": (c_size_t, [c_int]),
     "rlt_reward_any_loss": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    # evaluation in any cut reward (csrc/reward_eval.hip)
+    "rlt_reward_eval_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "rlt_reward_eval": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_cut_metrics_ex": (c_int, [P, P, P, c_int, c_int, c_double, P, P, P, P, P]),
     "rlt_mt_terms_workspace": (c_size_t, [c_int, c_int]),
     "rlt_mt_terms": (c_int, [P, P, P, c_int, c_int, c_float, P, P, c_size_t, P]),

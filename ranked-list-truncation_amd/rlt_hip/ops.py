@@ -1418,6 +1418,61 @@ def reward_spec_matrix(labels, spec, tau=1.0, want_q=False):
     return (r, q) if want_q else r
 
 
+def reward_eval(labels=None, spec=None, r=None, k=None, allow_empty=True, acc=None, per_list=True, split=True):
+    """One evaluation pass over a reward row (rlt_reward_eval).  The reward: `labels` (B,S) + `spec` (utils.rewards.RewardSpec),
+    or `r`, a (B,S) fp32 matrix.  k: (B,T) / (B,) int32 cuts of T rules or systems on the same lists, or None.  Returns
+    (per-list dict, acc): the dict holds best (B) fp32 and best_k (B) int32 - the row's largest reward over kmin..S, kmin = 0 with
+    allow_empty, and its first position - and, with cuts, r_at (B,T) fp32 and better (B,T) int32 (empty with per_list=False);
+    acc is the dict of float64 split sums curve (S+1), best_hist (S+1), sums (3 + 3T: lists, sum best, clamped cuts, then per
+    cut sum r_at, #(r_at == best), sum better) - pass the dict of an earlier call back as `acc` and this batch is ADDED into it;
+    with split=False no split sum is formed and acc is None (`acc` must then be None too).  Tensors in and out, no host read."""
+    if (labels is None) == (r is None) or (labels is None) != (spec is None):
+        raise ValueError("reward_eval: the reward is labels + spec, or a matrix r")
+    rows = N.f32c(labels if r is None else r)
+    N.require_cuda(rows, k)
+    if rows.dim() != 2:
+        raise ValueError(f"reward_eval: rows must be (B,S); got {tuple(rows.shape)}")
+    B, S = rows.shape
+    dev = rows.device
+    T = 0
+    if k is not None:
+        k = k.reshape(B, -1)
+        k = k if k.dtype == torch.int32 and k.is_contiguous() else k.to(torch.int32).contiguous()
+        T = int(k.shape[1])
+        if not 1 <= T <= N.SWEEP_MAX_T:
+            raise ValueError(f"reward_eval: {T} cuts per list, outside 1..{N.SWEEP_MAX_T}")
+    struct = keep = table = None
+    if spec is not None:
+        struct, keep = spec.native(S, dev)
+        table = dcg_table(dev) if struct.family == N.REWARD_GAIN and struct.discount is None else None
+    accumulate = acc is not None
+    if accumulate and not split:
+        raise ValueError("reward_eval: an accumulator was passed with split=False")
+    if split and not accumulate:
+        acc = {"curve": torch.zeros((S + 1,), dtype=torch.float64, device=dev),
+               "best_hist": torch.zeros((S + 1,), dtype=torch.float64, device=dev),
+               "sums": torch.zeros((3 + 3 * T,), dtype=torch.float64, device=dev)}
+    elif accumulate and (acc["curve"].numel() != S + 1 or acc["sums"].numel() != 3 + 3 * T):
+        raise ValueError(f"reward_eval: lists of {S} positions with {T} cuts do not fit the accumulator")
+    out = {}
+    if per_list:
+        out = {"best": torch.empty((B,), dtype=torch.float32, device=dev), "best_k": torch.empty((B,), dtype=torch.int32, device=dev)}
+        if T:
+            out["r_at"] = torch.empty((B, T), dtype=torch.float32, device=dev)
+            out["better"] = torch.empty((B, T), dtype=torch.int32, device=dev)
+    if not out and acc is None:
+        raise ValueError("reward_eval: nothing asked for (per_list=False, split=False)")
+    o = lambda n: ptr(out.get(n))
+    s = lambda n: ptr(acc[n]) if acc is not None else None
+    ws_bytes = query("rlt_reward_eval_workspace", B, S, T)
+    ws = workspace(ws_bytes, dev)
+    call("rlt_reward_eval", ptr(rows) if r is None else None, None if struct is None else N.ctypes.byref(struct),
+         ptr(rows) if r is not None else None, B, S, ptr(k), T, int(bool(allow_empty)), ptr(table), int(accumulate),
+         o("r_at"), o("better"), o("best"), o("best_k"), s("curve"), s("best_hist"), s("sums"), ptr(ws), ws_bytes, stream())
+    del keep
+    return out, acc
+
+
 # ------------------------------------------------------------------------------ optimizer
 def grad_norm(flat_grad, offsets=None, max_norm=None, state=None):
     """rlt_grad_norm on a flat fp32 gradient bucket (numel % 4 == 0, on the GPU) in one read; no host synchronisation.

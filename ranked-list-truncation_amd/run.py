@@ -385,8 +385,32 @@ class Trainer:
                 self.writer.add_scalar('baseline/Greedy_k_kDCG', k_dcg, L)
             else:
                 logging.info('\tBaseline Greedy-k (S = {}): no train lists of this length, skipped'.format(L))
+            spec = eval_reward_spec(self.args)
+            if spec is not None:                # --eval-reward: the same three rows in that reward
+                rec['reward'] = self._reward_baselines(spec, L, y_train, y_test, ks)
             out[str(L)] = rec
         return out
+
+    def _reward_baselines(self, spec, L, y_train, y_test, ks):
+        """Oracle / Fixed-k / Greedy-k of one list length in the reward `spec` (utils.baselines.RewardCurves): logged, written
+        to the scalar log under baseline/..._reward and returned as a dict."""
+        from utils.baselines import RewardCurves
+        test = RewardCurves(L, spec, self.device).update(y_test)
+        rec = {'spec': eval_reward_text(spec), 'Oracle': test.best_cut(), 'fixed_k': {}}
+        logging.info('\tBaseline Oracle (S = {}): reward = {:.6f} ({})'.format(L, rec['Oracle'], rec['spec']))
+        self.writer.add_scalar('baseline/Oracle_reward', rec['Oracle'], L)
+        for k in ks:
+            if 0 <= k <= L:
+                rec['fixed_k'][str(k)] = test.fixed_k(k)
+                logging.info('\tBaseline Fixed-k (S = {}, k = {}): reward = {:.6f}'.format(L, k, rec['fixed_k'][str(k)]))
+                self.writer.add_scalar('baseline/Fixed_k{}_reward'.format(k), rec['fixed_k'][str(k)], L)
+        if y_train is not None:
+            k = RewardCurves(L, spec, self.device).update(y_train).best_k()
+            rec['greedy_k'] = {'k': k, 'reward': test.fixed_k(k)}
+            logging.info('\tBaseline Greedy-k (S = {}, k = {}): reward = {:.6f}'.format(L, k, rec['greedy_k']['reward']))
+            self.writer.add_scalar('baseline/Greedy_k_reward', rec['greedy_k']['reward'], L)
+            self.writer.add_scalar('baseline/Greedy_k_kreward', k, L)
+        return rec
 
     def _split_batches(self, split):
         """(length, qids, x, y) of every bucket of a split in file order (no shuffling); BicutData keeps the same buckets."""
@@ -414,8 +438,9 @@ class Trainer:
         from utils.report import CutReport
         arrays, summaries, per_len = {}, {}, {}
         qid_all, len_all = [], []
+        spec = eval_reward_spec(self.args) if labelled else None
         for L, qids, x, y in self._split_batches(split):
-            rep = CutReport(L, metric=report_metric(self.args.criterion), device=self.device)
+            rep = CutReport(L, metric=report_metric(self.args.criterion), device=self.device, reward=spec)
             for i in range(0, x.shape[0], self.batch_size):
                 cut = self._forward_eval(x[i:i + self.batch_size])
                 rep.update(cut, y[i:i + self.batch_size] if labelled else None)
@@ -432,7 +457,10 @@ class Trainer:
             summaries[str(L)] = summ
             logging.info('\tReport ({} split, S = {}): {}'.format(split, L, json.dumps(summ)))
             for key, v in summ.items():
-                self.writer.add_scalar('report/{}'.format(key), v, L)
+                if not isinstance(v, str):
+                    self.writer.add_scalar('report/{}'.format(key), v, L)
+        if spec is not None:                    # the reward the reward columns are in: compare_reports(metric='reward') checks it
+            per_len["reward_spec"] = np.asarray(eval_reward_text(spec))
         np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
                  summary=np.asarray(json.dumps(summaries)), **{k: np.concatenate(v) for k, v in arrays.items()}, **per_len)
         return summaries
@@ -444,7 +472,7 @@ class Trainer:
         fresh = path if path.endswith(".npz") else path + ".npz"
         lines = []
         for other in [o for o in others.split(",") if o]:
-            cmp = compare_reports([other, fresh], metric=report_metric(self.args.criterion), baseline=0,
+            cmp = compare_reports([other, fresh], metric=compare_metric(self.args), baseline=0,
                                   resamples=10000, seed=self.args.seed or 0, device=self.device)
             lines += cmp.lines()
         for line in lines:
@@ -461,7 +489,10 @@ class Trainer:
         from utils.report import CutReport
         from utils.sweep import CutSweep, score_quantiles
         rule, thresholds = spec if isinstance(spec, tuple) else parse_cut_sweep(spec)
-        metric = self.args.criterion if self.args.criterion in ("f1", "dcg") else "f1"
+        metric = argmax_metric = self.args.criterion if self.args.criterion in ("f1", "dcg") else "f1"
+        reward = eval_reward_spec(self.args)
+        if reward is not None:                  # --eval-reward: tau* on the mean reward of the cuts; the argmax report keeps F1 / DCG
+            metric = "reward"
         buckets = {split: {L: (x, y) for L, _q, x, y in self._split_batches(split)} for split in ("train", "test")}
         results, arrays = {}, {}
         for L, (x_te, y_te) in buckets["test"].items():
@@ -471,9 +502,9 @@ class Trainer:
             x_tr, y_tr = buckets["train"][L]
             th = score_quantiles(x_tr[..., 0].cpu().numpy(), thresholds) if isinstance(thresholds, int) else thresholds
             sweeps = {}
-            argmax = None if rule == "score" else CutReport(L, metric=metric, device=self.device)
+            argmax = None if rule == "score" else CutReport(L, metric=argmax_metric, device=self.device, reward=reward)
             for split, (x, y) in (("train", (x_tr, y_tr)), ("test", (x_te, y_te))):
-                sw = CutSweep(L, rule, th, device=self.device)
+                sw = CutSweep(L, rule, th, device=self.device, reward=reward)
                 for i in range(0, x.shape[0], self.batch_size):
                     xb, yb = x[i:i + self.batch_size], y[i:i + self.batch_size]
                     v = xb[..., 0].to(self.device, non_blocking=True) if rule == "score" else self._forward_eval(xb)
@@ -486,11 +517,12 @@ class Trainer:
                    "n_test": sweeps["test"].n_lists, "train": sweeps["train"].at(tau), "test": sweeps["test"].at(tau)}
             if argmax is not None:
                 summ = argmax.summary()
-                rec["argmax"] = {"f1": summ["f1"], "dcg": summ["dcg"], "k": summ["mean_k"]}
+                rec["argmax"] = {"f1": summ["f1"], "dcg": summ["dcg"], "k": summ["mean_k"],
+                                 **({"reward": summ["reward"]} if reward is not None else {})}
             for split, sw in sweeps.items():
                 c = sw.curve()
                 arrays[f"thresholds_{L}"] = c["thresholds"]
-                for name in ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut"):
+                for name in ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut") + (("reward",) if reward is not None else ()):
                     arrays[f"{split}_{name}_{L}"] = c[name]
                 if split == "test":
                     for t, kk, f1, dcg in zip(c["thresholds"], c["k"], c["f1"], c["dcg"]):
@@ -588,6 +620,32 @@ def log_grad_guard(writer, optimizer, epoch):
     return {tag.split('/', 1)[1]: (v if math.isfinite(v) else None) for tag, v in zip(GRAD_GUARD_TAGS, vals)}
 
 
+def eval_reward_spec(args):
+    """--eval-reward -> the RewardSpec the baselines, the report, the comparison and the sweep also evaluate in, or None (off,
+    the default).  'criterion' is the run's own reward and an error under f1 / dcg, which those tools already speak."""
+    text = getattr(args, "eval_reward", None)       # (drivers build their own Namespace)
+    if not text:
+        return None
+    if text == "criterion":
+        if not RewardSpec.is_spec(args.criterion):
+            raise ValueError("--eval-reward criterion needs a --criterion beside f1 / dcg (fbeta:<beta>, ndcg, gain:...); "
+                             "F1 and DCG are reported as they are")
+        text = args.criterion
+    return RewardSpec.parse(text)
+
+
+def eval_reward_text(spec):
+    try:
+        return str(spec)
+    except ValueError:                              # a reward with its own discounts has no text form
+        return repr(spec)
+
+
+def compare_metric(args):
+    """The column --compare-to compares: 'reward' under --eval-reward, otherwise report_metric's."""
+    return 'reward' if eval_reward_spec(args) is not None else report_metric(args.criterion)
+
+
 def report_metric(criterion):
     """The metric of the cut report, the comparison and --draw, which know F1 and DCG: the run's criterion, or F1 under a reward
     beside those two (utils/rewards.py)."""
@@ -644,6 +702,11 @@ def build_parser():
     p.add_argument('--compare-to', type=str, default=None,
                    help="A.npz[,B.npz]: after --report-out, rank 0 compares the fresh report with each named one query by query "
                         "(paired randomization test, bootstrap interval, sign and t statistics) and logs one line per file")
+    p.add_argument('--eval-reward', type=str, default=None, metavar='criterion|SPEC',
+                   help="also evaluate in a cut reward beside F1 / DCG: 'criterion' (the run's own --criterion, which must then be a "
+                        "reward spec) or a spec (fbeta:<beta>, ndcg[:<penalty>], gain:<g0>,<g1>,...[:norm]).  --baselines 1 adds "
+                        "Oracle / Fixed-k / Greedy-k in that reward, --report-out writes reward, best_reward, best_reward_k and "
+                        "better_reward per query, --compare-to and --cut-sweep use the reward.  Default: off")
     p.add_argument('--report-split', type=str, default='test', choices=('train', 'test'))
     p.add_argument('--report-labels', type=int, default=1, choices=(0, 1), help="0: label-free report (k, winning value, margin only)")
     p.add_argument('--cut-sweep', type=parse_cut_sweep, default=None, metavar='RULE:LO:HI:N',
@@ -697,7 +760,12 @@ def apply_conf(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        eval_reward_spec(args)
+    except ValueError as e:
+        parser.error(str(e))
     # RLT_FORCE_DIST=1: initialise the process group (and run the step's collectives) even with one rank - the RCCL
     # rehearsal on a one-GPU box (rlt_hip/parallel.py)
     if (int(os.environ.get("WORLD_SIZE", "1")) > 1 or (FORCE_COLLECTIVES and "RANK" in os.environ)) and not dist.is_initialized():
@@ -729,7 +797,10 @@ def main(argv=None):
             fin = lambda v: v if v is not None and math.isfinite(v) else None     # -inf (no test epoch) is not valid JSON
             json.dump({"history": trainer.history, "best_f1": fin(trainer.best_test_f1), "best_dcg": fin(trainer.best_test_dcg),
                        "best5_f1": fin(trainer.best5_f1), "best5_dcg": fin(trainer.best5_dcg), "best_epoch": trainer.best_epoch,
-                       "world": trainer.world, **({"baselines": trainer.baseline_results} if args.baselines else {})}, f)
+                       "world": trainer.world, **({"baselines": trainer.baseline_results} if args.baselines else {}),
+                       **({"eval_reward": {"spec": eval_reward_text(eval_reward_spec(args)),
+                                           "report": getattr(trainer, "report_results", None),
+                                           "cut_sweep": getattr(trainer, "sweep_results", None)}} if eval_reward_spec(args) else {})}, f)
     if args.param_dump_dir:
         import numpy as np
         os.makedirs(args.param_dump_dir, exist_ok=True)

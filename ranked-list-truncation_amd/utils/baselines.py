@@ -8,6 +8,9 @@
   Truncation_analysis.ipynb  TruncationCurves.f1_curve() / dcg_curve() (mean over lists for each k = 0..S) and
                              irrelevant_share() (`countp`: share of irrelevant documents in each prefix, k = 1..S)
 
+  (no notebook)              RewardCurves / best_cut_reward / fixed_k_reward / greedy_k_reward: the same three rows in ANY cut
+                             reward (utils.rewards.RewardSpec: F_beta, graded gain, nDCG) from rlt_reward_eval
+
 Semantics are the notebooks' cal_F1 / cal_DCG in float64 (include/rlt_hip.h, rlt_truncation_curves): labels (B, S) 0/1 in rank
 order, F1@k = 2pr / (p + r) with p = c_k / k, r = c_k / N; DCG@k = sum_{i<k} (label == 1 ? 1 : penalty) / log2(i + 2); k = 0 is
 an entry of every curve with value 0, so a list's best DCG is never negative.  One difference: where the train curve's best F1 cut
@@ -113,6 +116,87 @@ class TruncationCurves:
         f1 = self.f1_curve().cpu().numpy()
         dcg = self.dcg_curve().cpu().numpy()
         return int(np.argmax(f1)), int(np.argmax(dcg))
+
+
+class RewardCurves:
+    """TruncationCurves in any cut reward: running sums of r[b,k], k = 0..S (r[b,0] = 0), and of each list's best reward, for
+    lists of S positions under a RewardSpec.  allow_empty=False takes the best over k = 1..S, the range the losses train on."""
+
+    def __init__(self, S, spec, device=None, allow_empty=True):
+        from utils.rewards import RewardSpec
+        S = int(S)
+        if not 1 <= S <= 1024:
+            raise ValueError(f"list length {S} outside 1..1024")
+        self.S, self.spec, self.allow_empty = S, RewardSpec.parse(spec), bool(allow_empty)
+        self.device = _dev(device)
+        self._acc = None
+        self._n = 0
+
+    def update(self, labels):
+        y = _labels(labels, self.device)
+        if y.shape[1] != self.S:
+            raise ValueError(f"lists of {y.shape[1]} positions, this accumulator holds {self.S}")
+        if y.shape[0]:
+            _, self._acc = ops.reward_eval(y, self.spec, allow_empty=self.allow_empty, acc=self._acc, per_list=False)
+            self._n += int(y.shape[0])
+        return self
+
+    @property
+    def n_lists(self):
+        return self._n
+
+    def curve(self):
+        """Mean reward at k over the lists, k = 0..S: (S+1,) float64 on the device."""
+        if not self._n:
+            raise ValueError("no lists have been added")
+        return self._acc["curve"] / self._n
+
+    def best_hist(self):
+        """How many lists have their best cut at k, k = 0..S: (S+1,) float64 on the device."""
+        if not self._n:
+            raise ValueError("no lists have been added")
+        return self._acc["best_hist"]
+
+    def best_cut(self):
+        """The Oracle row in this reward: the mean over the lists of each list's best reward."""
+        if not self._n:
+            raise ValueError("no lists have been added")
+        s = self._acc["sums"].tolist()
+        return s[1] / s[0]
+
+    def fixed_k(self, k):
+        """The mean reward when every list is cut at k, 0 <= k <= S."""
+        k = int(k)
+        if not 0 <= k <= self.S:
+            raise ValueError(f"cut position {k} outside 0..{self.S}")
+        return float(self.curve()[k])
+
+    def best_k(self):
+        """The first maximum of the mean curve over kmin..S (np.argmax), kmin = 0 with allow_empty."""
+        c = self.curve().cpu().numpy()
+        return int(np.argmax(c)) if self.allow_empty else int(np.argmax(c[1:])) + 1
+
+
+def _reward_curves(labels, spec, device, allow_empty):
+    y = _labels(labels, _dev(device))
+    return RewardCurves(y.shape[1], spec, y.device, allow_empty).update(y)
+
+
+def best_cut_reward(labels, spec, device=None, allow_empty=True):
+    """The Oracle row in the reward `spec`: the mean over the lists of labels (B, S) of the best reward any cut achieves."""
+    return _reward_curves(labels, spec, device, allow_empty).best_cut()
+
+
+def fixed_k_reward(labels, k, spec, device=None):
+    """The Fixed-k row in the reward `spec`: the mean reward when every list is cut at k."""
+    return _reward_curves(labels, spec, device, True).fixed_k(k)
+
+
+def greedy_k_reward(train_labels, test_labels, spec, device=None, allow_empty=True):
+    """The Greedy-k row in the reward `spec`: k* = the first maximum of the train split's mean reward curve, then the test
+    split's mean reward at k*.  Returns (reward, k*)."""
+    k = _reward_curves(train_labels, spec, device, allow_empty).best_k()
+    return _reward_curves(test_labels, spec, device, allow_empty).fixed_k(k), k
 
 
 def _curves(labels, penalty, device):

@@ -148,12 +148,14 @@ class PairedComparison:
 def _load_report(path, metric):
     with np.load(path, allow_pickle=False) as z:
         if metric not in z.files:
-            raise ValueError(f"{path}: no '{metric}' column (a label-free report cannot be compared)")
+            raise ValueError(f"{path}: no '{metric}' column (a label-free report cannot be compared)" if metric != "reward" else
+                             f"{path}: no 'reward' column (the report was written without --eval-reward)")
         keys = [(str(q), int(l)) for q, l in zip(z["qid"], z["length"])]
         cols = {k: np.asarray(z[k], dtype=np.float64) for k in (metric, "best_" + metric) if k in z.files}
+        spec = str(z["reward_spec"]) if "reward_spec" in z.files else None
     if len(set(keys)) != len(keys):
         raise ValueError(f"{path}: duplicate (qid, length) rows")
-    return keys, cols
+    return keys, cols, spec
 
 
 def is_best_cut(baseline):
@@ -165,15 +167,21 @@ def is_best_cut(baseline):
 
 def compare_reports(paths, metric="f1", baseline=0, resamples=10000, seed=0, device="cuda", keep_stats=True):
     """Load `run.py --report-out` files, join them on (qid, length) and compare.  baseline: an index into `paths`, or the name of the
-    Oracle baseline in any letter case (the first file's best_f1 / best_dcg column; every file is then a system).  Files whose query sets differ are refused."""
-    if metric not in ("f1", "dcg"):
-        raise ValueError("metric: 'f1' or 'dcg'")
+    Oracle baseline in any letter case (the first file's best_f1 / best_dcg column; every file is then a system).  Files whose query sets differ are refused.
+    metric='reward' reads the `reward` / `best_reward` columns a report written with a reward spec carries (CutReport(reward=...),
+    run.py --eval-reward); files without the column, and files whose `reward_spec` strings differ, are refused."""
+    if metric not in ("f1", "dcg", "reward"):
+        raise ValueError("metric: 'f1', 'dcg' or 'reward'")
     paths = list(paths)
     loaded = [_load_report(p, metric) for p in paths]
+    if metric == "reward":
+        for p, (_k, _c, spec) in zip(paths, loaded):
+            if spec != loaded[0][2]:
+                raise ValueError(f"{p}: its rewards are in {spec!r}, {paths[0]}'s in {loaded[0][2]!r}: not comparable")
     keys0 = loaded[0][0]
     ref = set(keys0)
     columns = []
-    for p, (keys, cols) in zip(paths, loaded):
+    for p, (keys, cols, _spec) in zip(paths, loaded):
         if set(keys) != ref:
             missing, extra = len(ref - set(keys)), len(set(keys) - ref)
             raise ValueError(f"{p}: its query set differs from {paths[0]}'s ({missing} missing, {extra} unknown)")

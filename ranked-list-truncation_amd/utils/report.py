@@ -22,7 +22,7 @@ _METRICS = {"f1": N.METRIC_F1, "dcg": N.METRIC_DCG}
 class CutReport:
     """Running report over lists of S positions: update() with batches, then per_query() / curves() / summary()."""
 
-    def __init__(self, S, metric="f1", penalty=-1.0, metric_penalty=-1.0, tau=0.9, sharpen=None, device=None):
+    def __init__(self, S, metric="f1", penalty=-1.0, metric_penalty=-1.0, tau=0.9, sharpen=None, device=None, reward=None):
         S = int(S)
         if not 1 <= S <= 1024:
             raise ValueError(f"list length {S} outside 1..1024")
@@ -35,7 +35,13 @@ class CutReport:
         self.tau = float(tau)
         self.sharpen = self.tau * 1e-3 if sharpen is None else float(sharpen)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        # reward: a RewardSpec (or its text form) - every list's cut is also valued in that reward (rlt_reward_eval)
+        self.reward = None
+        if reward is not None:
+            from utils.rewards import RewardSpec
+            self.reward = RewardSpec.parse(reward)
         self._acc = None
+        self._racc = None
         self._parts = []
         self._n = 0
         self._labelled = None
@@ -57,6 +63,11 @@ class CutReport:
             labels = torch.as_tensor(labels).to(self.device, non_blocking=True)
         per, self._acc = ops.cut_report(cut, labels, _METRICS[self.metric], self.penalty, self.metric_penalty, self.tau,
                                         self.sharpen, acc=self._acc)
+        if self.reward is not None and labels is not None:
+            # the k the pass above just wrote goes straight back in: device memory, no host read
+            ev, self._racc = ops.reward_eval(N.f32c(labels), self.reward, k=per["k"], allow_empty=False, acc=self._racc)
+            per.update({"reward": ev["r_at"].reshape(-1), "best_reward": ev["best"], "best_reward_k": ev["best_k"],
+                        "better_reward": ev["better"].reshape(-1)})
         self._parts.append(per)
         self._n += int(cut.shape[0])
         return self
@@ -71,7 +82,8 @@ class CutReport:
 
     def per_query(self):
         """{name: numpy array over the lists in the order they were added}: k, p_k, margin and, with labels, f1, dcg, best_f1,
-        best_f1_k, best_dcg, best_dcg_k, better."""
+        best_f1_k, best_dcg, best_dcg_k, better; with `reward=` also reward (the reward at k), best_reward, best_reward_k (the
+        list's best over k = 1..S and its first position) and better_reward (cuts 1..S that earn strictly more)."""
         self._need()
         return {n: torch.cat([p[n] for p in self._parts]).cpu().numpy() for n in self._parts[0]}
 
@@ -105,4 +117,18 @@ class CutReport:
                         "regret_f1": (s[2] - s[0]) / n, "regret_dcg": (s[3] - s[1]) / n,
                         "best_cut_share_f1": float(np.mean(q["k"] == q["best_f1_k"])),
                         "best_cut_share_dcg": float(np.mean(q["k"] == q["best_dcg_k"]))})
+            if self._racc is not None:
+                r = self._racc["sums"].tolist()         # lists, sum best, clamped cuts, sum reward, #(reward == best), sum better
+                out.update({"reward_spec": self.reward_text(), "reward": r[3] / r[0], "best_reward": r[1] / r[0],
+                            "regret_reward": (r[1] - r[3]) / r[0], "best_cut_share_reward": r[4] / r[0],
+                            "better_reward": r[5] / r[0]})
         return out
+
+    def reward_text(self):
+        """str(spec) of the report's reward, None without one (a reward with its own discounts: its repr)."""
+        if self.reward is None:
+            return None
+        try:
+            return str(self.reward)
+        except ValueError:
+            return repr(self.reward)

@@ -19,6 +19,7 @@ from rlt_hip import native as N
 from rlt_hip import ops
 
 METRICS = ("f1", "dcg", "precision", "recall", "fbeta")
+REWARD = "reward"               # the metric name of a sweep that was given a reward spec
 
 
 def parse_sweep(spec):
@@ -56,7 +57,7 @@ def score_quantiles(scores, n):
 class CutSweep:
     """Running effectiveness / cost curve of T thresholds of one cut rule over lists of S positions."""
 
-    def __init__(self, S, rule, thresholds, penalty=-1, beta=1, device=None):
+    def __init__(self, S, rule, thresholds, penalty=-1, beta=1, device=None, reward=None):
         S = int(S)
         if not 1 <= S <= 1024:
             raise ValueError(f"list length {S} outside 1..1024")
@@ -70,7 +71,13 @@ class CutSweep:
         self.penalty, self.beta = float(penalty), float(beta)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._thr = torch.from_numpy(self.thresholds).to(self.device)
+        # reward: a RewardSpec (or its text form) - the (B,T) cuts of every batch are also valued in it (rlt_reward_eval)
+        self.reward = None
+        if reward is not None:
+            from utils.rewards import RewardSpec
+            self.reward = RewardSpec.parse(reward)
         self._curve = None
+        self._racc = None
         self._n = 0
 
     def update(self, values, labels):
@@ -83,7 +90,10 @@ class CutSweep:
             return self
         v = v.detach().to(self.device, non_blocking=True)
         labels = torch.as_tensor(labels).to(self.device, non_blocking=True)
-        _, self._curve = ops.cut_sweep(v, self._thr, self.rule, labels, self.penalty, self.beta, curve=self._curve, want_k=False)
+        k, self._curve = ops.cut_sweep(v, self._thr, self.rule, labels, self.penalty, self.beta, curve=self._curve,
+                                       want_k=self.reward is not None)
+        if self.reward is not None:             # the sweep's cuts go straight back in: device memory, no host read
+            _, self._racc = ops.reward_eval(N.f32c(labels), self.reward, k=k, allow_empty=True, acc=self._racc, per_list=False)
         self._n += int(v.shape[0])
         return self
 
@@ -105,12 +115,19 @@ class CutSweep:
         out = {"thresholds": self.thresholds.copy(), "n": self._n}
         for i, name in enumerate(N.SWEEP_ROWS[:7]):
             out[name] = s[i] / n
+        if self._racc is not None:
+            r = self._racc["sums"].cpu().numpy()            # lists, sum best, clamped cuts, then 3 per threshold
+            out[REWARD] = r[3::3] / r[0]
+            out["best_reward"] = float(r[1] / r[0])
         return out
+
+    def _metrics(self):
+        return METRICS + ((REWARD,) if self.reward is not None else ())
 
     def best(self, metric="f1"):
         """(tau*, its index, the mean `metric` there): the first maximum over the thresholds in the order they were given."""
-        if metric not in METRICS:
-            raise ValueError(f"metric {metric!r}: one of {METRICS}")
+        if metric not in self._metrics():
+            raise ValueError(f"metric {metric!r}: one of {self._metrics()}")
         row = self.curve()[metric]
         i = int(np.argmax(row))
         return float(self.thresholds[i]), i, float(row[i])
@@ -122,14 +139,18 @@ class CutSweep:
             raise ValueError(f"{tau} is not one of this sweep's thresholds")
         c = self.curve()
         i = int(hit[0])
-        return {"tau": float(self.thresholds[i]), "index": i, **{n: float(c[n][i]) for n in N.SWEEP_ROWS[:7]}}
+        return {"tau": float(self.thresholds[i]), "index": i, **{n: float(c[n][i]) for n in N.SWEEP_ROWS[:7]},
+                **({REWARD: float(c[REWARD][i])} if self.reward is not None else {})}
 
 
-def tune_cut_rule(train_batches, test_batches, rule, thresholds, S=None, metric="f1", penalty=-1, beta=1, device=None):
+def tune_cut_rule(train_batches, test_batches, rule, thresholds, S=None, metric="f1", penalty=-1, beta=1, device=None, reward=None):
     """Pick tau* on the training split, report the test split there.  train_batches / test_batches: iterables of (values,
     labels) as CutSweep.update takes them.  Returns a dict: tau, index, train (the figures at tau* on the training split), test
-    (on the test split), train_curve and test_curve (CutSweep.curve())."""
-    if metric not in METRICS:
+    (on the test split), train_curve and test_curve (CutSweep.curve()).  reward: a RewardSpec - tau* is then picked on the mean
+    reward of the cuts (`metric` is 'reward'), and every figure gains a `reward` entry beside the F1 / DCG / F_beta ones."""
+    if reward is not None:
+        metric = REWARD
+    elif metric not in METRICS:
         raise ValueError(f"metric {metric!r}: one of {METRICS}")
     sweeps = []
     for batches in (train_batches, test_batches):
@@ -137,7 +158,7 @@ def tune_cut_rule(train_batches, test_batches, rule, thresholds, S=None, metric=
         for values, labels in batches:
             if sw is None:
                 v = values[-1] if isinstance(values, (list, tuple)) else values
-                sw = CutSweep(v.shape[1] if S is None else S, rule, thresholds, penalty, beta, device)
+                sw = CutSweep(v.shape[1] if S is None else S, rule, thresholds, penalty, beta, device, reward=reward)
             sw.update(values, labels)
         if sw is None or not sw.n_lists:
             raise ValueError("tune_cut_rule: a split without lists")

@@ -1157,6 +1157,67 @@ def reward_any(shapes=((4096, 300), (1048576, 300)), reps=9):
         torch.cuda.empty_cache()
 
 
+def reward_eval(shapes=((1048576, 300),), cuts=(1, 19), reps=9):
+    """rlt_reward_eval (nDCG built from the labels, every output on) against the best composition of what existed before it:
+    rlt_reward_spec_matrix for the (B,S) reward, then torch - sum(0) in float64 for the curve, max(1) for the best cut, gather at
+    the cuts, compare-and-count for `better`, bincount for the histogram.  HIP events around single alternating launches, the
+    median of `reps`; GB/s on the pass's algorithmic bytes, 4 S + 4 T per list."""
+    from utils.rewards import RewardSpec
+    spec = RewardSpec.ndcg()
+    for B, S in shapes:
+        g = torch.Generator(device=dev).manual_seed(11)
+        prob = 0.55 * torch.exp(-torch.arange(S, dtype=torch.float32, device=dev) / 45.0) + 0.02
+        y = (torch.rand(B, S, device=dev, generator=g) < prob).float()
+        for T in cuts:
+            k = torch.randint(0, S + 1, (B, T), device=dev, generator=g, dtype=torch.int32)
+            k64 = k.long()
+            res = {}
+
+            def fused():
+                res["fused"] = ops.reward_eval(y, spec, k=k, allow_empty=True)
+
+            def composed():
+                r = ops.reward_spec_matrix(y, spec)
+                full = torch.cat([torch.zeros(B, 1, device=dev), r], 1)
+                curve = full.sum(0, dtype=torch.float64)
+                best, best_k = full.max(1)
+                r_at = full.gather(1, k64)
+                better = torch.stack([(full > r_at[:, t:t + 1]).sum(1, dtype=torch.int32) for t in range(T)], 1)
+                hist = torch.bincount(best_k, minlength=S + 1)
+                sums = (best.sum(dtype=torch.float64), r_at.sum(0, dtype=torch.float64), (r_at == best[:, None]).sum(0),
+                        better.sum(0, dtype=torch.float64))
+                res["composed"] = (curve, best, best_k, r_at, better, hist, sums)
+            fns = (("rlt_reward_eval, every output", fused), ("rlt_reward_spec_matrix + torch composition", composed))
+            for _name, fn in fns:
+                fn()
+            torch.cuda.synchronize()
+            out, acc = res["fused"]
+            curve, best, best_k, r_at, better, hist, _sums = res["composed"]
+            assert torch.equal(out["r_at"], r_at) and torch.equal(out["best"], best) and torch.equal(out["better"], better)
+            assert torch.equal(acc["best_hist"], hist.double()) and torch.allclose(acc["curve"], curve, rtol=1e-12)
+            times = {name: [] for name, _fn in fns}
+            for _ in range(reps):
+                for name, fn in fns:
+                    res.clear()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn()
+                    b.record()
+                    torch.cuda.synchronize()
+                    times[name].append(a.elapsed_time(b))
+            nbytes = (4.0 * S + 4.0 * T) * B
+            med = {name: sorted(v)[reps // 2] for name, v in times.items()}
+            for name, v in times.items():
+                print(f"reward_eval B{B} S{S} T{T} {name:44s}: {med[name] * 1e3:10.1f} us (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f}, "
+                      f"{reps} calls)  {nbytes / med[name] / 1e6:8.1f} GB/s on 4 S + 4 T bytes per list", flush=True)
+            names = [n for n, _ in fns]
+            print(f"reward_eval B{B} S{S} T{T} composition / fused: {med[names[1]] / med[names[0]]:.2f}x"
+                  + ("  (the fused pass is SLOWER than the composition here)" if med[names[0]] > med[names[1]] else ""), flush=True)
+            res.clear()
+            del k, k64, out, acc, curve, best, best_k, r_at, better, hist
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
