@@ -24,10 +24,6 @@
 #include <stdlib.h>
 #include <utility>
 
-#ifndef RLT_A6_DKV_PREFETCH
-#define RLT_A6_DKV_PREFETCH 0   // dK+dV kernel, 1: next tile's global loads issued BEFORE the tile body (32 staging registers live across it); measured 48.9 ms against 47.6 with the loads after the body (the partner workgroup covers their latency)
-#endif
-
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -678,11 +674,6 @@ __global__ __launch_bounds__(256, 2) void attn6_bwd_dkv_kernel(AttnArgs a) {
     __syncthreads();
 
     for (int t = 0; t < nt; ++t) {
-        if (!IMG && RLT_A6_DKV_PREFETCH && t + 1 < nt) {
-            stage6_load<HD>(base, ld, (t + 1) * KT, B, tid, rq);
-            stage6_load<HD>(dobase, (size_t)E, (t + 1) * KT, B, tid, rd);
-            load_small((t + 1) * KT);
-        }
         if (wave_live) {
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
@@ -715,7 +706,9 @@ __global__ __launch_bounds__(256, 2) void attn6_bwd_dkv_kernel(AttnArgs a) {
                 mma_cols6<HD>(Qi, sub, lane, dp, dk);                        // dK^T[d][key] += Q^T dS
             }
         }
-        if (!IMG && !RLT_A6_DKV_PREFETCH && t + 1 < nt) {       // no registers held across the tile body; the partner workgroup covers the latency
+        // next tile's global loads AFTER the tile body: no staging registers held across it, the partner workgroup covers the latency
+        // (issued before the body, with 32 registers live across it: measured 48.9 ms against 47.6)
+        if (!IMG && t + 1 < nt) {
             stage6_load<HD>(base, ld, (t + 1) * KT, B, tid, rq);
             stage6_load<HD>(dobase, (size_t)E, (t + 1) * KT, B, tid, rd);
             load_small((t + 1) * KT);
@@ -761,46 +754,121 @@ struct Frag2 { bf16x8 h, m; };
 // LDS tile image of the two one-wavefront kernels below (they stage and split their tiles themselves, so the layout is theirs alone):
 // [plane][64 rows][64 d] bf16 with 128-byte rows, the 16-byte unit c of row r at c ^ swz1(r).  The padded 144-byte rows of the other kernels
 // of this file cost these two 21-27 % of their LDS cycles in bank conflicts (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r06_notes.md:
-// the transposed reads of four rows x 64 bytes wrap onto each other at a 36-bank stride); this one is conflict-free for the row fragments
-// (`ds_read_b128`: 16-lane groups of rows {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} at one unit), the transposed fragments
+// the transposed reads of four rows x 64 bytes wrap onto each other at a 36-bank stride; launch times were the same); this one is conflict-free
+// for the row fragments (`ds_read_b128`: 16-lane groups of rows {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} at one unit), the transposed fragments
 // (`ds_read_b64_tr_b16`: 4 rows x 4 units per 32 lanes) and the staging stores (a row per 16 lanes) - tests/test_a6h_layout.py enumerates it.
-// RLT_A6_SWZ=0 (build switch): the padded layout (A/B runs).
-#ifndef RLT_A6_SWZ
-#define RLT_A6_SWZ 1
-#endif
-constexpr int LDR1 = RLT_A6_SWZ ? 64 : ldr6<64>(), PL1 = KT * LDR1, IMG1 = 3 * PL1;
+constexpr int LDR1 = 64, PL1 = KT * LDR1, IMG1 = 3 * PL1;
 __host__ __device__ constexpr int swz1(int row) { return (((row >> 1) & 1) << 2) | ((row >> 3) & 3); }
 // element offset of bf16 element `col` (a multiple of 4) of row `row` in a plane
-__device__ __forceinline__ int img1_off(int row, int col) {
-#if RLT_A6_SWZ
-    return row * 64 + ((((col >> 3) ^ swz1(row)) << 3) | (col & 7));
-#else
-    return row * LDR1 + col;
-#endif
+__device__ __forceinline__ int img1_off(int row, int col) { return row * LDR1 + ((((col >> 3) ^ swz1(row)) << 3) | (col & 7)); }
+
+// ---- what the tile-body lambdas of both kernels are made of.  The dK+dV kernel's names stand for both: the STATIONARY operands are a
+// wavefront's own rows (K and V; Q and dO in the dQ kernel), the TILE images the rows it loops over (Q and dO; K and V).
+// Staging unit i of a thread = the four floats at d = 4 (idx % 16) of tile row idx / 16, idx = tid + 256 i.  Its three planes -> image:
+__device__ __forceinline__ void store_unit1(uint16_t* img, int tid, int i, uint2 h, uint2 m, uint2 l) {
+    const int idx = tid + 256 * i;
+    const int off = img1_off(idx / 16, 4 * (idx % 16));
+    *reinterpret_cast<uint2*>(img + off) = h;
+    *reinterpret_cast<uint2*>(img + PL1 + off) = m;
+    *reinterpret_cast<uint2*>(img + 2 * PL1 + off) = l;
 }
-// prologue staging of a whole tile into that layout (the tile body stages through its generated chunks)
+// prologue staging of a whole tile (the tile body stages through its generated chunks)
 __device__ __forceinline__ void stage1_store(uint16_t* __restrict__ img, int tid, const Stage6<64>& st) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int idx = tid + 256 * i;
         uint2 h, m, l;
         split4x3_6(st.v[i].x, st.v[i].y, st.v[i].z, st.v[i].w, h, m, l);
-        const int off = img1_off(idx / 16, 4 * (idx % 16));
-        *reinterpret_cast<uint2*>(img + off) = h;
-        *reinterpret_cast<uint2*>(img + PL1 + off) = m;
-        *reinterpret_cast<uint2*>(img + 2 * PL1 + off) = l;
+        store_unit1(img, tid, i, h, m, l);
     }
 }
-#ifndef RLT_A6_MLAST
-#define RLT_A6_MLAST 0     // 1: the plane of the first product is read LAST so that one wait covers a step - measured 1 % slower
-#endif
-#ifndef RLT_A6_ACCV
-#define RLT_A6_ACCV 1      // S / dP products of the one-wavefront kernels as asm MFMAs with VGPR accumulators (0: builtins, A/B switch)
-#endif
-#ifndef RLT_DKV1_PIN
-#define RLT_DKV1_PIN 1
-#endif
+// Global load of staging unit i of the tile at row0.  Rows beyond B repeat the last row (finite values) and there is no select here - it
+// would wait for the load where it is issued: in the dK+dV kernel the lse entry of such a row is +inf, so P = dS = 0 and nothing reaches
+// dK / dV; the dQ kernel zeroes its K rows where it splits them.  32-bit element offset from the (uniform) matrix base: B * ld < 2^24
+// (host-checked for these two kernels), one v_mad_u32_u24 instead of a 64-bit multiply per load
+__device__ __forceinline__ float4 load_unit1(const float* src, size_t ld, int row0, int B, int tid, int i) {
+    const int idx = tid + 256 * i;
+    const uint32_t off = __umul24((uint32_t)min(row0 + idx / 16, B - 1), (uint32_t)ld) + 4u * (uint32_t)(idx % 16);
+    return *reinterpret_cast<const float4*>(src + off);
+}
+// part `part` of the split of staging unit i; behind the last part its planes go to `img` and its registers take the same unit of the
+// tile at next_row0 of next_src
+__device__ __forceinline__ void stage_part1(Split6& sg, float4& r, int part, uint16_t* img, int tid, int i, const float* next_src, size_t next_ld,
+                                            int next_row0, int B) {
+    split6_part(sg, r.x, r.y, r.z, r.w, part);
+    if (part == 5) {
+        store_unit1(img, tid, i, sg.hi, sg.mid, sg.lo);
+        r = load_unit1(next_src, next_ld, next_row0, B, tid, i);
+    }
+}
+// part `part` of the split of rows 16 s + 4 half .. + 3 of the element-wise results w
+__device__ __forceinline__ void split_part1(Split6& u, const float (&w)[16], int s, int half, int part) {
+    const int r0 = 8 * s + 4 * half;
+    split6_part(u, w[r0], w[r0 + 1], w[r0 + 2], w[r0 + 3], part);
+}
+// At the top of the tile loop: keeps the accumulator blocks in AGPRs across the back edge (without it hipcc shares their registers with
+// the S / dP accumulators and moves 64 of them out and back every tile), and the stationary fragments whose only uses are "a"
+// operands of mfma_v with them (with dK / dV that is 224 of the 256)
+template <class T> __device__ __forceinline__ void pin_agpr(T& x) { asm volatile("" : "+a"(x)); }
+// LDS read k of X step j of block b (issued one step ahead): the row fragment of the tile image (S steps j < 4: img_s, dP steps: img_p)
+// and the stationary l fragment of the step.  Issue order m, l, h, stationary l - the order in which the products first take them;
+// LDS reads complete in order, so the first three products each wait for one read more.  The plane of the first product LAST, so that
+// one wait covers the whole step: measured 1 % slower.
+__device__ __forceinline__ void read_x1(int k, int b, int j, int l31, int hh, const uint16_t* img_s, const uint16_t* img_p, const uint4* lplane,
+                                        Frag3& afr, uint4& lfr) {
+    const uint16_t* img = j < 4 ? img_s : img_p;
+    const int off = img1_off((b >> 1) * 32 + l31, 8 * hh + 16 * (j & 3));
+    if (k == 3) lfr = lplane[((b & 1) * 4 + j) * 64];
+    else if (k == 2) afr.h = *reinterpret_cast<const bf16x8*>(img + off);
+    else if (k == 1) afr.l = *reinterpret_cast<const bf16x8*>(img + 2 * PL1 + off);
+    else afr.m = *reinterpret_cast<const bf16x8*>(img + PL1 + off);
+}
+// LDS read k (of six: planes m, l, h x two row groups) of a Y step: `img` transposed, rows 16 s .. 16 s + 15 of sub-tile `sub`, d tile dt
+__device__ __forceinline__ void read_y1(int k, int sub, int s, int dt, int lane, int hh, const uint16_t* img, v4s (&trv)[3][2]) {
+    const int row = sub * 32 + 16 * s + 4 * hh + ((lane & 15) >> 2) + 8 * (k & 1);
+    const int off = img1_off(row, 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
+    const int pl = k < 2 ? 1 : k < 4 ? 2 : 0;
+    trv[pl][k & 1] = tr_read6(img + pl * PL1 + off);
+}
+// operands of product i of a Y step: the transposed fragment; the split units of the two halves of a k-step (BY VALUE: through
+// references hipcc promotes u0 to registers too late, a widened 16-byte load keeps it in scratch - 64 stores and 37 loads per tile body)
 __device__ __forceinline__ bf16x8 cat2_6(uint2 a, uint2 b) { return __builtin_bit_cast(bf16x8, make_uint4(a.x, a.y, b.x, b.y)); }
+__device__ __forceinline__ bf16x8 y_frag_a(const v4s (&trv)[3][2], int i) { return cat_frag6(trv[x6_plane_a(i)][0], trv[x6_plane_a(i)][1]); }
+__device__ __forceinline__ bf16x8 y_frag_b(const Split6 u0, const Split6 u1, int i) {
+    const int bp = x6_plane_b(i);
+    return bp == 0 ? cat2_6(u0.hi, u1.hi) : bp == 1 ? cat2_6(u0.mid, u1.mid) : cat2_6(u0.lo, u1.lo);
+}
+// The S / dP products as asm statements: accumulator in VGPRs (the element-wise chunks read it there - as a builtin hipcc puts it into
+// AGPRs and every element costs a v_accvgpr_read), stationary fragments in AGPRs where b_agpr (pin_agpr).  hipcc does not see an MFMA in
+// the asm and inserts no wait states for it: the accumulator is first read ACC_LAG = 3 gaps (3 MFMAs + their chunks: > 11 wait states)
+// behind the last product (tools/gen_attn6_body.py); a product never follows a vector write of its operands (fragments come from LDS /
+// the setup).
+__device__ __forceinline__ void mfma_v(f32x16& c, bf16x8 av, bf16x8 bv, bool zero, bool b_agpr) {
+    if (zero) {
+        if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "a"(bv));
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
+    } else {
+        if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "a"(bv));
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
+    }
+}
+// product i of X step j: S (j < 4) takes the stationary fragments f1 (h, m: AGPRs; l: the LDS read lfr), dP the fragments f2 (AGPRs: all
+// three planes if f2_agpr, else only h)
+__device__ __forceinline__ void mx1(f32x16& sc, f32x16& dp, const Frag3& a, const uint4& lfr, const Frag2 (&f1)[4], const Frag3 (&f2)[4], int i, int j,
+                                    bool f2_agpr) {
+    const int ap = x6_plane_a(i), bp = x6_plane_b(i);
+    const bf16x8 av = ap == 0 ? a.h : ap == 1 ? a.m : a.l;
+    if (j < 4) {
+        if (bp == 2) mfma_v(sc, av, __builtin_bit_cast(bf16x8, lfr), false, false);
+        else mfma_v(sc, av, bp == 0 ? f1[j].h : f1[j].m, j == 0 && i == 0, true);
+    } else {
+        const Frag3& vv = f2[j - 4];
+        mfma_v(dp, av, bp == 0 ? vv.h : bp == 1 ? vv.m : vv.l, j == 4 && i == 0, f2_agpr || bp == 0);
+    }
+}
+// component r & 3 of a float4 / uint4 table read
+template <class V> __device__ __forceinline__ auto comp4(const V& v, int r) -> decltype(v.x) {
+    return (r & 3) == 0 ? v.x : (r & 3) == 1 ? v.y : (r & 3) == 2 ? v.z : v.w;
+}
 #ifdef RLT_DKV1_STAMPS
 // diagnostic build only: s_memtime at every step of tiles 8..11 of one workgroup (tools/bench_kernels.py dkv1_stamps); entries 64 /
 // 65: before / behind the barrier
@@ -810,9 +878,16 @@ __device__ unsigned long long dkv1_stamps[4 * 4 * 66];
 #else
 #define DKV1_STAMP(k) do { } while (0)
 #endif
+// what the generated bodies use besides the kernels' lambdas mx, my, rx, ry, tl, te, ea, eb, sp, stg
+#define GAP_END __builtin_amdgcn_sched_barrier(0)
+#define ATTN6_STAMP DKV1_STAMP
+// (asking for the finished S / dP accumulators in VGPRs here - asm("" : "+v"(sc)) - makes hipcc copy all 16 registers in one
+// burst behind the last MFMA; left to itself it reads each register where its chunk needs it, one v_accvgpr_read per element)
+#define ACC_DONE(w) do { } while (0)
+
 template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
-    constexpr int HD = 64, IMG6 = IMG1, PL = PL1;
+    constexpr int HD = 64, IMG6 = IMG1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);              // [2 buffers][Q image | dO image]
     float* tab0 = reinterpret_cast<float*>(img0 + 4 * IMG6);         // [2 buffers][lse * log2e | delta | row hashes][KT]
@@ -870,15 +945,6 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
         tb[KT + trow] = re;
         if (DROP) reinterpret_cast<uint32_t*>(tb)[2 * KT + trow] = rlt_row_hash(ps, (uint32_t)(row0 + trow));
     };
-    auto load_unit = [&](const float* src, size_t lds_, int row0, int i) {
-        const int idx = tid + 256 * i;
-        const int row = row0 + idx / (HD / 4), dq_ = idx % (HD / 4);
-        // rows beyond B repeat the last row (finite values): their lse entry is +inf, so P = dS = 0 and nothing reaches dK / dV;
-        // no select here - it would wait for the load where it is issued.  32-bit element offset from the (uniform) matrix
-        // base: B * ld < 2^24 (host-checked for this kernel), one v_mad_u32_u24 instead of a 64-bit multiply per load
-        const uint32_t off = __umul24((uint32_t)min(row, B - 1), (uint32_t)lds_) + 4u * (uint32_t)dq_;
-        rs.v[i] = *reinterpret_cast<const float4*>(src + off);
-    };
     // prologue: tile 0 -> buffer 0; Q of tile 1 -> staging registers, lse / delta of tile 1 -> rl / re
     {
         Stage6<HD> r0;
@@ -905,23 +971,17 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
         float* Tn = tab0 + (cur ^ 1) * 3 * KT;
         const int row_n1 = min(t + 1, nt - 1) * KT, row_n2 = min(t + 2, nt - 1) * KT;
 
-#if RLT_DKV1_PIN
-        // (keeps the eight accumulator blocks in AGPRs across the back edge: without it hipcc shares their registers with the
-        // S / dP accumulators and moves 64 of them out and back every tile)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            asm volatile("" : "+a"(dk[i >> 1][i & 1]));
-            asm volatile("" : "+a"(dv[i >> 1][i & 1]));
+            pin_agpr(dk[i >> 1][i & 1]);
+            pin_agpr(dv[i >> 1][i & 1]);
         }
-#if RLT_A6_ACCV
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            asm volatile("" : "+a"(kf[i >> 2][i & 3].h));
-            asm volatile("" : "+a"(kf[i >> 2][i & 3].m));
-            asm volatile("" : "+a"(vf[i >> 2][i & 3].h));
+            pin_agpr(kf[i >> 2][i & 3].h);
+            pin_agpr(kf[i >> 2][i & 3].m);
+            pin_agpr(vf[i >> 2][i & 3].h);
         }
-#endif
-#endif
         f32x16 sc, dp;                               // S / dP accumulators of the block in its X phase
         float pv[16], gv[16];                        // P (dropped) and dS of the block whose splits are under way
         Split6 st[2][2][2];                          // [P | dS][k-step][half]: the split units (state and result)
@@ -931,31 +991,10 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
         uint4 klr[2];
         float4 lvr[2], evr[2];
         uint4 hvr[2];
-#define GAP_END __builtin_amdgcn_sched_barrier(0)
-#define ATTN6_STAMP DKV1_STAMP
-// (asking for the finished S / dP accumulators in VGPRs here - asm("" : "+v"(sc)) - makes hipcc copy all 16 registers in one
-// burst behind the last MFMA; left to itself it reads each register where its chunk needs it, one v_accvgpr_read per element)
-#define ACC_DONE(w) do { } while (0)
-        // LDS read k of step j of X(b) / Y(b) into buffer u (issued one step ahead)
-        auto rx = [&](int u, int k, int b, int j) __attribute__((always_inline)) {
-            const int sub = b >> 1, kh = b & 1;
-            const uint16_t* img = j < 4 ? Qc : Dc;
-            const int off = img1_off(sub * 32 + l31, 8 * hh + 16 * (j & 3));
-            // issue order: the plane the FIRST product takes (m) LAST - LDS reads complete in order, so the one wait in front of
-            // that product covers the whole step (issued m, l, h: a wait before each of the first three products)
-            const int kk = RLT_A6_MLAST ? (j < 4 ? k : k + 1) : (k < 3 ? 3 - k : 0);
-            if (kk == 0) klr[u] = klr_base[(kh * 4 + j) * 64];
-            else if (kk == 1) afr[u].h = *reinterpret_cast<const bf16x8*>(img + off);
-            else if (kk == 2) afr[u].l = *reinterpret_cast<const bf16x8*>(img + 2 * PL + off);
-            else afr[u].m = *reinterpret_cast<const bf16x8*>(img + PL + off);
-        };
+        // block b = (query sub-tile b >> 1, key half b & 1); u: the fragment buffer.  Y step j = (k-step j >> 2, dV | dK, d tile j & 1)
+        auto rx = [&](int u, int k, int b, int j) __attribute__((always_inline)) { read_x1(k, b, j, l31, hh, Qc, Dc, klr_base, afr[u], klr[u]); };
         auto ry = [&](int u, int k, int b, int j) __attribute__((always_inline)) {
-            const int sub = b >> 1, s = j >> 2, which = (j >> 1) & 1, dt = j & 1;
-            const uint16_t* img = which ? Qc : Dc;
-            const int row = sub * 32 + 16 * s + 4 * hh + ((lane & 15) >> 2) + 8 * (k & 1);
-            const int off = img1_off(row, 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
-            const int pl = RLT_A6_MLAST ? (k < 2 ? 0 : k < 4 ? 2 : 1) : (k < 2 ? 1 : k < 4 ? 2 : 0);     // h, l, m: the plane of the first product last
-            trv[u][pl][k & 1] = tr_read6(img + pl * PL + off);
+            read_y1(k, b >> 1, j >> 2, j & 1, lane, hh, (j >> 1) & 1 ? Qc : Dc, trv[u]);
         };
         auto tl = [&](int b, int c) __attribute__((always_inline)) {
             lvr[c & 1] = *reinterpret_cast<const float4*>(Tc + (b >> 1) * 32 + 8 * c + 4 * hh);
@@ -964,66 +1003,19 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
             evr[c & 1] = *reinterpret_cast<const float4*>(Tc + KT + (b >> 1) * 32 + 8 * c + 4 * hh);
             if (DROP) hvr[c & 1] = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint32_t*>(Tc) + 2 * KT + (b >> 1) * 32 + 8 * c + 4 * hh);
         };
-        // product i of a step: (a.m, b.m), (a.l, b.h), (a.h, b.l), (a.m, b.h), (a.h, b.m), (a.h, b.h); planes 0 h, 1 m, 2 l
-        // The S / dP products as asm statements: accumulator in VGPRs (the element-wise chunks read it there - as a builtin hipcc
-        // puts it into AGPRs and every element costs a v_accvgpr_read), the K fragments and the h plane of V in AGPRs ("a": their
-        // only uses, pinned at the loop top; with dK / dV that is 224 of the 256).  hipcc does not see an MFMA in the asm and
-        // inserts no wait states for it: the accumulator is first read ACC_LAG = 3 gaps (3 MFMAs + their chunks: > 11 wait
-        // states) behind the last product (tools/gen_attn6_body.py); a product never follows a vector write of its operands
-        // (fragments come from LDS / the setup).
-        auto mfma_v = [&](f32x16& c, bf16x8 av, bf16x8 bv, bool zero, bool b_agpr) __attribute__((always_inline)) {
-#if !RLT_A6_ACCV
-            f32x16 z;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, zero ? z : c, 0, 0, 0);
-            return;
-#endif
-            if (zero) {
-                if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "a"(bv));
-                else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
-            } else {
-                if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "a"(bv));
-                else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-            }
-        };
-        auto mx = [&](int u, int i, int b, int j) __attribute__((always_inline)) {
-            const int kh = b & 1;
-            const int ap = i == 0 || i == 3 ? 1 : i == 1 ? 2 : 0, bp = i == 0 || i == 4 ? 1 : i == 2 ? 2 : 0;
-            const bf16x8 av = ap == 0 ? afr[u].h : ap == 1 ? afr[u].m : afr[u].l;
-            if (j < 4) {
-                if (bp == 2) mfma_v(sc, av, __builtin_bit_cast(bf16x8, klr[u]), false, false);
-                else mfma_v(sc, av, bp == 0 ? kf[kh][j].h : kf[kh][j].m, j == 0 && i == 0, true);
-            } else {
-                const Frag3& vv = vf[kh][j - 4];
-                if (bp == 0) mfma_v(dp, av, vv.h, false, true);
-                else mfma_v(dp, av, bp == 1 ? vv.m : vv.l, j == 4 && i == 0, false);
-            }
-        };
+        auto mx = [&](int u, int i, int b, int j) __attribute__((always_inline)) { mx1(sc, dp, afr[u], klr[u], kf[b & 1], vf[b & 1], i, j, false); };
         auto my = [&](int u, int i, int b, int j) __attribute__((always_inline)) {
             const int kh = b & 1, s = j >> 2, which = (j >> 1) & 1, dt = j & 1;
-            const int ap = i == 0 || i == 3 ? 1 : i == 1 ? 2 : 0, bp = i == 0 || i == 4 ? 1 : i == 2 ? 2 : 0;
-            const bf16x8 av = cat_frag6(trv[u][ap][0], trv[u][ap][1]);
-            const Split6& u0 = st[which][s][0];
-            const Split6& u1 = st[which][s][1];
-            const bf16x8 bv = bp == 0 ? cat2_6(u0.hi, u1.hi) : bp == 1 ? cat2_6(u0.mid, u1.mid) : cat2_6(u0.lo, u1.lo);
-            if (which == 0) dv[kh][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, dv[kh][dt], 0, 0, 0);
-            else dk[kh][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, dk[kh][dt], 0, 0, 0);
+            f32x16& acc = which == 0 ? dv[kh][dt] : dk[kh][dt];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(y_frag_a(trv[u], i), y_frag_b(st[which][s][0], st[which][s][1], i), acc, 0, 0, 0);
         };
         // register r of block b: P = exp2(S - lse) / dS = P (dP - delta) and the dropout of P
-        auto ea = [&](int b, int r) __attribute__((always_inline)) {
-            const float4& l4 = lvr[(r >> 2) & 1];
-            const float lv = (r & 3) == 0 ? l4.x : (r & 3) == 1 ? l4.y : (r & 3) == 2 ? l4.z : l4.w;
-            pv[r] = rlt_exp2(sc[r] - lv);
-        };
+        auto ea = [&](int b, int r) __attribute__((always_inline)) { pv[r] = rlt_exp2(sc[r] - comp4(lvr[(r >> 2) & 1], r)); };
         auto eb = [&](int b, int r) __attribute__((always_inline)) {
-            const float4& e4 = evr[(r >> 2) & 1];
-            const float ev = (r & 3) == 0 ? e4.x : (r & 3) == 1 ? e4.y : (r & 3) == 2 ? e4.z : e4.w;
+            const float ev = comp4(evr[(r >> 2) & 1], r);
             float dpr = dp[r];
             if (DROP) {
-                const uint4& h4 = hvr[(r >> 2) & 1];
-                const uint32_t hv = (r & 3) == 0 ? h4.x : (r & 3) == 1 ? h4.y : (r & 3) == 2 ? h4.z : h4.w;
-                const float m = rlt_keep_rc(hv, (b & 1) ? hk1 : hk0, a.drop_thr) ? inv_keep : 0.f;
+                const float m = rlt_keep_rc(comp4(hvr[(r >> 2) & 1], r), (b & 1) ? hk1 : hk0, a.drop_thr) ? inv_keep : 0.f;
                 dpr *= m;
                 gv[r] = pv[r] * (dpr - ev);
                 pv[r] *= m;
@@ -1031,25 +1023,11 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
                 gv[r] = pv[r] * (dpr - ev);
             }
         };
-        auto sp = [&](int m, int s, int half, int part) __attribute__((always_inline)) {
-            const float* w = m ? gv : pv;
-            const int r0 = 8 * s + 4 * half;
-            split6_part(st[m][s][half], w[r0], w[r0 + 1], w[r0 + 2], w[r0 + 3], part);
-        };
-        // staging unit i (rows idx / 16 of the tile): which = 0: Q of tile t + 1 -> image, then load dO of tile t + 1 into the same
-        // registers; which = 1: dO of tile t + 1 -> image, then load Q of tile t + 2
+        auto sp = [&](int m, int s, int half, int part) __attribute__((always_inline)) { split_part1(st[m][s][half], m ? gv : pv, s, half, part); };
+        // staging unit i: which = 0: Q of tile t + 1 -> image, then load dO of tile t + 1 into the same registers; which = 1: dO of
+        // tile t + 1 -> image, then load Q of tile t + 2
         auto stg = [&](int which, int i, int part) __attribute__((always_inline)) {
-            split6_part(sg[i], rs.v[i].x, rs.v[i].y, rs.v[i].z, rs.v[i].w, part);
-            if (part == 5) {
-                uint16_t* img = which ? Dn : Qn;
-                const int idx = tid + 256 * i;
-                const int off = img1_off(idx / (HD / 4), 4 * (idx % (HD / 4)));
-                *reinterpret_cast<uint2*>(img + off) = sg[i].hi;
-                *reinterpret_cast<uint2*>(img + PL + off) = sg[i].mid;
-                *reinterpret_cast<uint2*>(img + 2 * PL + off) = sg[i].lo;
-                if (which == 0) load_unit(dobase, (size_t)E, row_n1, i);
-                else load_unit(base, ld, row_n2, i);
-            }
+            stage_part1(sg[i], rs.v[i], part, which ? Dn : Qn, tid, i, which ? base : dobase, which ? ld : (size_t)E, which ? row_n2 : row_n1, B);
         };
         store_small(Tn, row_n1);                     // lse / delta of tile t + 1 (loaded during tile t - 1)
         load_small(row_n2);
@@ -1060,9 +1038,6 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
         } else {
 #include "attention6_dkv1_body.inc"
         }
-#undef GAP_END
-#undef ATTN6_STAMP
-#undef ACC_DONE
         DKV1_STAMP(64);
         __syncthreads();
         DKV1_STAMP(65);
@@ -1086,7 +1061,7 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dkv1_kernel(AttnArgs a) {
 // zeros, so whatever dS they get multiplies a zero column of K^T - no mask on the scores.
 template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
-    constexpr int HD = 64, IMG6 = IMG1, PL = PL1;
+    constexpr int HD = 64, IMG6 = IMG1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);              // [2 buffers][K image | V image]
     uint32_t* tab0 = reinterpret_cast<uint32_t*>(img0 + 4 * IMG6);   // [2 buffers][KT] column hashes of the tile's keys (DROP)
@@ -1132,12 +1107,6 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
     const int nt = rlt_cdiv_dev(B, KT);
     Stage6<HD> rs;                                                  // ONE staging set: K of the next tile, then V of the next tile, ...
     const int trow = tid & (KT - 1);
-    auto load_unit = [&](const float* src, int row0, int i) {
-        const int idx = tid + 256 * i;
-        const int row = row0 + idx / (HD / 4), dq_ = idx % (HD / 4);
-        const uint32_t off = __umul24((uint32_t)min(row, B - 1), (uint32_t)ld) + 4u * (uint32_t)dq_;     // (see attn6_bwd_dkv1_kernel)
-        rs.v[i] = *reinterpret_cast<const float4*>(src + off);
-    };
     {   // prologue: tile 0 -> buffer 0; K of tile 1 -> staging registers
         Stage6<HD> r0;
         stage6_load<HD>(base + E, ld, 0, B, tid, rs);               // (zero rows beyond B)
@@ -1147,7 +1116,7 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
         if (DROP) tab0[trow] = rlt_col_hash(ps, (uint32_t)trow);
         const int r1 = min(1, nt - 1) * KT;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) load_unit(base + E, r1, i);
+        for (int i = 0; i < 4; ++i) rs.v[i] = load_unit1(base + E, ld, r1, B, tid, i);
     }
     __syncthreads();
 
@@ -1162,17 +1131,15 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
         uint32_t* Tn = tab0 + (cur ^ 1) * KT;
         const int row_n1 = min(t + 1, nt - 1) * KT, row_n2 = min(t + 2, nt - 1) * KT;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" : "+a"(dq[i >> 1][i & 1]));     // (see attn6_bwd_dkv1_kernel)
-#if RLT_A6_ACCV
+        for (int i = 0; i < 4; ++i) pin_agpr(dq[i >> 1][i & 1]);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {               // the stationary fragments live in AGPRs (their only uses are "a" operands)
-            asm volatile("" : "+a"(qf[i >> 2][i & 3].h));
-            asm volatile("" : "+a"(qf[i >> 2][i & 3].m));
-            asm volatile("" : "+a"(dof[i >> 2][i & 3].h));
-            asm volatile("" : "+a"(dof[i >> 2][i & 3].m));
-            asm volatile("" : "+a"(dof[i >> 2][i & 3].l));
+        for (int i = 0; i < 8; ++i) {
+            pin_agpr(qf[i >> 2][i & 3].h);
+            pin_agpr(qf[i >> 2][i & 3].m);
+            pin_agpr(dof[i >> 2][i & 3].h);
+            pin_agpr(dof[i >> 2][i & 3].m);
+            pin_agpr(dof[i >> 2][i & 3].l);
         }
-#endif
         f32x16 sc, dp;                               // S^T / dP^T accumulators of the block in its X phase
         float pv[16], gv[16];                        // P and dS^T of the block whose element-wise work / splits are under way
         Split6 st[2][2][2];                          // [1][k-step][half]: the split units of dS^T (state and result)
@@ -1181,105 +1148,32 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
         v4s trv[2][3][2];
         uint4 qlr[2];
         uint4 hvr[2];
-#define GAP_END __builtin_amdgcn_sched_barrier(0)
-#define ATTN6_STAMP DKV1_STAMP
-// (asking for the finished S / dP accumulators in VGPRs here - asm("" : "+v"(sc)) - makes hipcc copy all 16 registers in one
-// burst behind the last MFMA; left to itself it reads each register where its chunk needs it, one v_accvgpr_read per element)
-#define ACC_DONE(w) do { } while (0)
-        auto rx = [&](int u, int k, int b, int j) __attribute__((always_inline)) {
-            const int sub = b >> 1, qh = b & 1;
-            const uint16_t* img = j < 4 ? Kc : Vc;
-            const int off = img1_off(sub * 32 + l31, 8 * hh + 16 * (j & 3));
-            const int kk = RLT_A6_MLAST ? (j < 4 ? k : k + 1) : (k < 3 ? 3 - k : 0);     // (m last: see attn6_bwd_dkv1_kernel)
-            if (kk == 0) qlr[u] = qlr_base[(qh * 4 + j) * 64];
-            else if (kk == 1) afr[u].h = *reinterpret_cast<const bf16x8*>(img + off);
-            else if (kk == 2) afr[u].l = *reinterpret_cast<const bf16x8*>(img + 2 * PL + off);
-            else afr[u].m = *reinterpret_cast<const bf16x8*>(img + PL + off);
-        };
-        auto ry = [&](int u, int k, int b, int j) __attribute__((always_inline)) {
-            const int sub = b >> 1, s = j >> 1, dt = j & 1;
-            const int row = sub * 32 + 16 * s + 4 * hh + ((lane & 15) >> 2) + 8 * (k & 1);
-            const int off = img1_off(row, 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
-            const int pl = RLT_A6_MLAST ? (k < 2 ? 0 : k < 4 ? 2 : 1) : (k < 2 ? 1 : k < 4 ? 2 : 0);
-            trv[u][pl][k & 1] = tr_read6(Kc + pl * PL + off);
-        };
+        // Y step j = (k-step j >> 1, d tile j & 1)
+        auto rx = [&](int u, int k, int b, int j) __attribute__((always_inline)) { read_x1(k, b, j, l31, hh, Kc, Vc, qlr_base, afr[u], qlr[u]); };
+        auto ry = [&](int u, int k, int b, int j) __attribute__((always_inline)) { read_y1(k, b >> 1, j >> 1, j & 1, lane, hh, Kc, trv[u]); };
         auto te = [&](int b, int c) __attribute__((always_inline)) {
             if (DROP) hvr[c & 1] = *reinterpret_cast<const uint4*>(Tc + (b >> 1) * 32 + 8 * c + 4 * hh);
         };
-        // The S^T / dP^T products as asm statements: accumulator in VGPRs (the element-wise chunks read it there - as a builtin
-        // hipcc puts it into AGPRs and every element costs a v_accvgpr_read), stationary fragments in AGPRs ("a": the only uses of
-        // qf / dof, so they live there).  hipcc does not see an MFMA in the asm and inserts no wait states for it: the
-        // accumulator is first read RLT_A6_ACC_LAG gaps (>= 3 MFMAs + their chunks: > 11 wait states) behind the last product
-        // (tools/gen_attn6_body.py), a product never follows a vector write of its operands (fragments come from LDS / setup).
-        auto mfma_v = [&](f32x16& c, bf16x8 av, bf16x8 bv, bool zero, bool b_agpr) __attribute__((always_inline)) {
-#if !RLT_A6_ACCV
-            f32x16 z;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = 0.f;
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, zero ? z : c, 0, 0, 0);
-            return;
-#endif
-            if (zero) {
-                if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "a"(bv));
-                else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(av), "v"(bv));
-            } else {
-                if (b_agpr) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "a"(bv));
-                else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-            }
-        };
-        auto mx = [&](int u, int i, int b, int j) __attribute__((always_inline)) {
-            const int qh = b & 1;
-            const int ap = i == 0 || i == 3 ? 1 : i == 1 ? 2 : 0, bp = i == 0 || i == 4 ? 1 : i == 2 ? 2 : 0;
-            const bf16x8 av = ap == 0 ? afr[u].h : ap == 1 ? afr[u].m : afr[u].l;
-            if (j < 4) {
-                if (bp == 2) mfma_v(sc, av, __builtin_bit_cast(bf16x8, qlr[u]), false, false);
-                else mfma_v(sc, av, bp == 0 ? qf[qh][j].h : qf[qh][j].m, j == 0 && i == 0, true);
-            } else {
-                const Frag3& vv = dof[qh][j - 4];
-                mfma_v(dp, av, bp == 0 ? vv.h : bp == 1 ? vv.m : vv.l, j == 4 && i == 0, true);
-            }
-        };
+        auto mx = [&](int u, int i, int b, int j) __attribute__((always_inline)) { mx1(sc, dp, afr[u], qlr[u], qf[b & 1], dof[b & 1], i, j, true); };
         auto my = [&](int u, int i, int b, int j) __attribute__((always_inline)) {
-            const int qh = b & 1, s = j >> 1, dt = j & 1;
-            const int ap = i == 0 || i == 3 ? 1 : i == 1 ? 2 : 0, bp = i == 0 || i == 4 ? 1 : i == 2 ? 2 : 0;
-            const bf16x8 av = cat_frag6(trv[u][ap][0], trv[u][ap][1]);
-            const Split6& u0 = st[1][s][0];
-            const Split6& u1 = st[1][s][1];
-            const bf16x8 bv = bp == 0 ? cat2_6(u0.hi, u1.hi) : bp == 1 ? cat2_6(u0.mid, u1.mid) : cat2_6(u0.lo, u1.lo);
-            dq[qh][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, dq[qh][dt], 0, 0, 0);
+            f32x16& acc = dq[b & 1][j & 1];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(y_frag_a(trv[u], i), y_frag_b(st[1][j >> 1][0], st[1][j >> 1][1], i), acc, 0, 0, 0);
         };
         auto ea = [&](int b, int r) __attribute__((always_inline)) { pv[r] = rlt_exp2(sc[r] - lse2[b & 1]); };
         auto eb = [&](int b, int r) __attribute__((always_inline)) {
             float dpr = dp[r];
-            if (DROP) {
-                const uint4& h4 = hvr[(r >> 2) & 1];
-                const uint32_t hv = (r & 3) == 0 ? h4.x : (r & 3) == 1 ? h4.y : (r & 3) == 2 ? h4.z : h4.w;
-                dpr = rlt_keep_rc((b & 1) ? hq1 : hq0, hv, a.drop_thr) ? dpr * inv_keep : 0.f;
-            }
+            if (DROP) dpr = rlt_keep_rc((b & 1) ? hq1 : hq0, comp4(hvr[(r >> 2) & 1], r), a.drop_thr) ? dpr * inv_keep : 0.f;
             gv[r] = pv[r] * (dpr - del[b & 1]);
         };
-        auto sp = [&](int m, int s, int half, int part) __attribute__((always_inline)) {
-            const int r0 = 8 * s + 4 * half;
-            split6_part(st[1][s][half], gv[r0], gv[r0 + 1], gv[r0 + 2], gv[r0 + 3], part);
-        };
+        auto sp = [&](int m, int s, int half, int part) __attribute__((always_inline)) { split_part1(st[1][s][half], gv, s, half, part); };
         // staging unit i: which = 0: K of tile t + 1 (rows beyond B as zeros) -> image, then load V of tile t + 1 into the same
         // registers; which = 1: V of tile t + 1 -> image, then load K of tile t + 2
         auto stg = [&](int which, int i, int part) __attribute__((always_inline)) {
-            const int idx = tid + 256 * i;
             if (which == 0 && part == 0) {
-                const bool ok = row_n1 + idx / (HD / 4) < B;
+                const bool ok = row_n1 + (tid + 256 * i) / (HD / 4) < B;
                 rs.v[i] = make_float4(ok ? rs.v[i].x : 0.f, ok ? rs.v[i].y : 0.f, ok ? rs.v[i].z : 0.f, ok ? rs.v[i].w : 0.f);
             }
-            split6_part(sg[i], rs.v[i].x, rs.v[i].y, rs.v[i].z, rs.v[i].w, part);
-            if (part == 5) {
-                uint16_t* img = which ? Vn : Kn;
-                const int off = img1_off(idx / (HD / 4), 4 * (idx % (HD / 4)));
-                *reinterpret_cast<uint2*>(img + off) = sg[i].hi;
-                *reinterpret_cast<uint2*>(img + PL + off) = sg[i].mid;
-                *reinterpret_cast<uint2*>(img + 2 * PL + off) = sg[i].lo;
-                if (which == 0) load_unit(base + 2 * E, row_n1, i);
-                else load_unit(base + E, row_n2, i);
-            }
+            stage_part1(sg[i], rs.v[i], part, which ? Vn : Kn, tid, i, base + (which ? E : 2 * E), ld, which ? row_n2 : row_n1, B);
         };
         if (DROP) Tn[trow] = rlt_col_hash(ps, (uint32_t)(row_n1 + trow));
         rx(0, 0, 0, 0); rx(0, 1, 0, 0); rx(0, 2, 0, 0); rx(0, 3, 0, 0);
@@ -1289,9 +1183,6 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
         } else {
 #include "attention6_dq1_body.inc"
         }
-#undef GAP_END
-#undef ATTN6_STAMP
-#undef ACC_DONE
         DKV1_STAMP(64);
         __syncthreads();
         DKV1_STAMP(65);
@@ -1302,6 +1193,9 @@ __global__ __launch_bounds__(256, 1) void attn6_bwd_dq1_kernel(AttnArgs a) {
         if (q < B) store_acc_T<HD>(a.dqkv + ((size_t)s_ * B + q) * ld + h * HD, hh, dq[qh], a.scale);
     }
 }
+#undef GAP_END
+#undef ATTN6_STAMP
+#undef ACC_DONE
 
 // ------------------------------------------------------------------------------------------ dQ
 template <int HD, bool DROP, bool IMG>

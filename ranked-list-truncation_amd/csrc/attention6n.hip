@@ -886,7 +886,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_bwd1_kernel(AttnArgs
             mma_av(which ? dp[it][kb] : sc[it][kb], sel[kb], plane(which, level - 1, it));
         };
         auto m_o = [&](int it, int n, int which, int k, int fb) __attribute__((always_inline)) {
-            const int ap = k == 0 || k == 3 ? 1 : k == 1 ? 2 : 0, bp = k == 0 || k == 4 ? 1 : k == 2 ? 2 : 0;
+            const int ap = x6_plane_a(k), bp = x6_plane_b(k);
             const int mat = DKV ? (which ? 0 : 1) : 0;          // dQ: K^T; dV: dO^T, dK: Q^T
             const int w = DKV ? which : 0;
             typedef short v8s __attribute__((ext_vector_type(8)));
@@ -1070,7 +1070,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs
             mma_av(sc[it][kb], sel[kb], plane(0, level - 1, it));
         };
         auto m_o = [&](int it, int n, int which, int k, int fb) __attribute__((always_inline)) {
-            const int ap = k == 0 || k == 3 ? 1 : k == 1 ? 2 : 0, bp = k == 0 || k == 4 ? 1 : k == 2 ? 2 : 0;
+            const int ap = x6_plane_a(k), bp = x6_plane_b(k);
             typedef short v8s __attribute__((ext_vector_type(8)));
             const v4s x = trf[fb][1][ap][0], y = trf[fb][1][ap][1];
             const v8s av = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};

@@ -4,6 +4,15 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+// The six plane products of a bf16x6 product a*b, smallest first: product i takes plane x6_plane_a(i) of the A operand and plane
+// x6_plane_b(i) of the B operand (0 = h, 1 = m, 2 = l).  The same order as PROD in tools/attn_pipe_sched.py, which the generated
+// tile bodies are scheduled for.
+__host__ __device__ constexpr int x6_plane_a(int i) { return i == 0 || i == 3 ? 1 : i == 1 ? 2 : 0; }
+__host__ __device__ constexpr int x6_plane_b(int i) { return i == 0 || i == 4 ? 1 : i == 2 ? 2 : 0; }
+static_assert(x6_plane_a(0) == 1 && x6_plane_b(0) == 1 && x6_plane_a(1) == 2 && x6_plane_b(1) == 0 && x6_plane_a(2) == 0 && x6_plane_b(2) == 2 &&
+              x6_plane_a(3) == 1 && x6_plane_b(3) == 0 && x6_plane_a(4) == 0 && x6_plane_b(4) == 1 && x6_plane_a(5) == 0 && x6_plane_b(5) == 0,
+              "(m, m) (l, h) (h, l) (m, h) (h, m) (h, h)");
+
 // The split written one instruction per asm statement in LEVEL order (both conversions, the four unpacks, the four subtractions,
 // ...), as six parts (4, 4, 4, 4, 4, 2 instructions) with its state, for kernels that hand the parts out one per MFMA gap: in
 // that order no instruction sits next to the one it depends on, and the 22 instructions vanish in the shadows of six MFMAs of the
