@@ -11,7 +11,11 @@
 //
 // Reverse sweep (P = row softmax of the row pass, Q = column softmax of the column pass; v_k does not depend on
 // v_{k-1}, nor u_k on u_{k-1}: the terms cancel):
-//   gC = pi (1 - C/eps);  gu_i = sum_j pi C / eps;  gv_j = sum_i pi C / eps
+//   c_j = sum_i pi C / sum_i pi;  gC = pi (1 - (C - c_j)/eps);  gu_i = sum_j pi (C - c_j) / eps;  gv_j = sum_i pi (C - c_j) / eps
+//   (the column sums of pi are the constant marginal after the column pass of iteration K, so sum_ij pi c_j is a constant
+//   and the gradient is that of sum_ij pi (C - c_j) with c held fixed.  Without the shift the seeds are of size pi C / eps
+//   and cancel down to O(pi) only inside gC, each carrying a float32 rounding of its full size: 3x to 35x the dp error of
+//   float32 autograd, worst where C_ij hardly depends on i.)
 //   for k = K..1:   gC_ij += gv_j Q_ij;  gu_i -= sum_j gv_j Q_ij;        (column pass of iteration k)
 //                   gC_ij += gu_i P_ij;  gv_j  = -sum_i gu_i P_ij;  gu = 0 (row pass of iteration k)
 //   dp_is = 2 sum_j gC_ij (p_is - y_js)
@@ -26,7 +30,7 @@ struct WassWs {
     float* C; float* gC;
     float* hu; float* hv;          // [max_iter+1][B]
     float* lrow; float* lcol;      // [max_iter+1][B]  LSE of the row / column pass of iteration k (index k)
-    float* du;                     // [B] |u_k - u_{k-1}|
+    float* du;                     // [B] |u_k - u_{k-1}|; after the last iteration: c_j, the column centres of the sweep's seeds
     float* gu; float* gv;          // [B]
     float* rowpart;                // [B] per-row partial of the final cost
     int* state;                    // [0] = done flag, [1] = iterations performed
@@ -144,45 +148,67 @@ __global__ __launch_bounds__(256) void wass_check_kernel(WassWs w, int B, int k,
         if (s < thresh) w.state[0] = 1;
     }
 }
-// final cost and the seeds of the reverse sweep; one workgroup per row
+// seeds of the reverse sweep, column side: c_j = sum_i pi C / sum_i pi (the centre of column j), gv_j = sum_i pi (C - c_j) / eps
+__global__ __launch_bounds__(256) void wass_final_col_kernel(WassWs w, int B, float eps) {
+    __shared__ float part[4][64], mass[4][64];
+    const int K = w.state[1];
+    const float* uK = w.hu + (size_t)K * B;
+    const float* vK = w.hv + (size_t)K * B;
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 64 + lane, rl = threadIdx.x >> 6;
+    float acc = 0.f, sp = 0.f;
+    if (j < B)
+        for (int i = rl; i < B; i += 4) {
+            const float c = w.C[(size_t)i * B + j];
+            const float pi = expf(((-c + uK[i]) + vK[j]) / eps);
+            acc += pi * c;
+            sp += pi;
+        }
+    part[rl][lane] = acc; mass[rl][lane] = sp;
+    __syncthreads();
+    const float tot = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    const float m = (mass[0][lane] + mass[1][lane]) + (mass[2][lane] + mass[3][lane]);
+    const float cj = m > 0.f ? tot / m : 0.f;
+    __syncthreads();
+    acc = 0.f;
+    if (j < B)
+        for (int i = rl; i < B; i += 4) {
+            const float c = w.C[(size_t)i * B + j];
+            acc += expf(((-c + uK[i]) + vK[j]) / eps) * (c - cj);
+        }
+    part[rl][lane] = acc;
+    __syncthreads();
+    if (rl == 0 && j < B) {
+        w.du[j] = cj;                            // du is free once the forward iterations are over
+        w.gv[j] = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / eps;
+    }
+}
+// final cost and the seeds of the reverse sweep, row side; one workgroup per row, after the column kernel (reads c_j from du)
 __global__ __launch_bounds__(256) void wass_final_row_kernel(WassWs w, int B, float eps) {
     __shared__ float sm[4];
     const int K = w.state[1], i = blockIdx.x;
     const float* uK = w.hu + (size_t)K * B;
     const float* vK = w.hv + (size_t)K * B;
     const float ui = uK[i];
-    float cost = 0.f;
+    float cost = 0.f, seed = 0.f;
     for (int j = threadIdx.x; j < B; j += 256) {
         const float c = w.C[(size_t)i * B + j];
+        const float ct = c - w.du[j];
         const float pi = expf(((-c + ui) + vK[j]) / eps);
         cost += pi * c;
-        w.gC[(size_t)i * B + j] = pi * (1.f - c / eps);
+        seed += pi * ct;
+        w.gC[(size_t)i * B + j] = pi * (1.f - ct / eps);
     }
     cost = block_sum(cost, sm);
-    if (threadIdx.x == 0) { w.rowpart[i] = cost; w.gu[i] = cost / eps; }
+    seed = block_sum(seed, sm);
+    if (threadIdx.x == 0) { w.rowpart[i] = cost; w.gu[i] = seed / eps; }
 }
-__global__ __launch_bounds__(256) void wass_final_col_kernel(WassWs w, int B, float eps, float* __restrict__ loss) {
-    __shared__ float part[4][64];
+// loss = sum of the row partials, one workgroup
+__global__ __launch_bounds__(256) void wass_loss_kernel(WassWs w, int B, float* __restrict__ loss) {
     __shared__ float sm[4];
-    const int K = w.state[1];
-    const float* uK = w.hu + (size_t)K * B;
-    const float* vK = w.hv + (size_t)K * B;
-    const int j = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
-    float acc = 0.f;
-    if (j < B)
-        for (int i = rl; i < B; i += 4) {
-            const float c = w.C[(size_t)i * B + j];
-            acc += expf(((-c + uK[i]) + vK[j]) / eps) * c;
-        }
-    part[rl][threadIdx.x & 63] = acc;
-    __syncthreads();
-    if (rl == 0 && j < B) w.gv[j] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x])) / eps;
-    if (blockIdx.x == 0) {                      // block 0 also sums the row partials into the loss
-        float s = 0.f;
-        for (int i = threadIdx.x; i < B; i += 256) s += w.rowpart[i];
-        s = block_sum(s, sm);
-        if (threadIdx.x == 0) *loss = s;
-    }
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) s += w.rowpart[i];
+    s = block_sum(s, sm);
+    if (threadIdx.x == 0) *loss = s;
 }
 // reverse of the column pass of iteration k (row-oriented): gC_ij += gv_j Q_ij; gu_i -= sum_j gv_j Q_ij
 __global__ __launch_bounds__(256) void wass_bwd_col_kernel(WassWs w, int B, int k, float eps) {
@@ -266,8 +292,9 @@ int rlt_wass_loss_fwd(const float* p, const float* labels, int B, int S, float e
         hipLaunchKernelGGL(wass_col_kernel, dim3(cb), dim3(256), 0, st, w, B, k, eps, logm);
         hipLaunchKernelGGL(wass_check_kernel, dim3(1), dim3(256), 0, st, w, B, k, thresh);
     }
+    hipLaunchKernelGGL(wass_final_col_kernel, dim3(cb), dim3(256), 0, st, w, B, eps);
     hipLaunchKernelGGL(wass_final_row_kernel, dim3(B), dim3(256), 0, st, w, B, eps);
-    hipLaunchKernelGGL(wass_final_col_kernel, dim3(cb), dim3(256), 0, st, w, B, eps, loss);
+    hipLaunchKernelGGL(wass_loss_kernel, dim3(1), dim3(256), 0, st, w, B, loss);
     return RLT_LAUNCH_RESULT();
 }
 
