@@ -561,7 +561,9 @@ int rlt_list_attention_bwd_dkv(const float* qkv, const float* dout, const float*
 int rlt_list_attention_bwd_dq(const float* qkv, const float* dout, const float* lse, const void* images, void* ws, size_t ws_bytes,
                               int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv, int precision, void* stream);
 /* What the entry points above decide for one call (csrc/attention_plan.h: the decision is taken once per call, there; tests:
- * tests/test_attention_plan.py, tests/test_attention_dispatch_gpu.py).  Host only: no device work, no influence on the choice.
+ * tests/test_attention_plan.py, tests/test_attention_dispatch_gpu.py; every eval-mode kernel at its tile edges with lse, delta, the
+ * fix-up flag words and the order of the backward parts: tests/test_attention_edges_gpu.py; the train-mode kernels:
+ * tests/test_dropout_gpu.py).  Host only: no device work, no influence on the choice.
  * have_images: the call is given a usable `images` buffer (non-NULL; for the pipelined forwards also 16-byte aligned and
  * images_bytes long).  Errors: RLT_E_ARG (out NULL, non-positive S / B / H, drop_p outside [0, 1), precision), RLT_E_SHAPE (HD).
  *   fwd, dkv, dq     the kernel of rlt_list_attention_fwd / _bwd_dkv / _bwd_dq, an RLT_ATTN_* code

@@ -2,7 +2,9 @@
 (tests/attn_plan_restate.py) that reaches it: the plan's kernel code is asserted first, then the forward and dQ / dK / dV are
 compared with the fp64 reference of tools/gpu_probe.py (_attn_ref; the same relative max-norm error and tolerances: 1e-5
 forward, 3e-5 gradients, 6x in bf16x3 mode).  NaN sentinels behind `images`, the workspace and dqkv must stay untouched.
-No environment switch is read or set: RLT_ATTN_X6_IMG / _X6_PP_IMG need RLT_ATTN6_IMG=1 and are pinned by the plan test only."""
+No environment switch is read or set: RLT_ATTN_X6_IMG / _X6_PP_IMG need RLT_ATTN6_IMG=1 and are pinned by the plan test only.
+One shape per kernel: the eval-mode kernels at their tile edges, lse, delta, the fix-up flag words and the order of the backward
+parts are tests/test_attention_edges_gpu.py; the train-mode kernels at theirs, tests/test_dropout_gpu.py."""
 import math
 
 import pytest
