@@ -1552,6 +1552,47 @@ __device__ __forceinline__ void vals6e(const float4 (&v)[4], int p, float& a, fl
     }
 }
 
+// RLT_GEMM_ACCUMULATE in gemm6e: C = relu?(fl(fl(acc + bias) + C)), the value the element-wise loop of write_output_simple gives.
+// Written as `v += base[loff]; base[loff] = v;` per element, the read of element r + 1 cannot be moved above the store of element r
+// (C may be any pointer and ldo is a run-time value), so the wavefront paid one full memory latency per accumulator register: 256
+// dependent load - wait - add - store round trips per tile, with no partner wavefront on the SIMD to run meanwhile.  Here the reads
+// are ordered by hand: the 16 C values of a 32 x 32 block are loaded together, and the next block's 16 are issued BEFORE this
+// block's stores, so one latency is exposed per call and the rest overlap the stores.  Every element is still read exactly once,
+// before its own store and by the lane that stores it, so C may be the buffer an earlier GEMM wrote (in place) - no aliasing promise
+// is made to the compiler.  (gemm6c keeps the element-wise form of write_output_t: its persistent form has no free registers -
+// batched there, the reads spilled - and its second wavefront per SIMD covers the round trips; profiles/accum_epilogue_notes.md)
+template <int NJ>
+__device__ __forceinline__ void accumulate_blocks(const GemmArgs& g, const f32x16 (&acc)[2][NJ], float* out, int ldo, int rb, int cb,
+                                                  int loff, int l31, bool relu) {
+    float bv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        bv[j] = 0.f;
+        if (g.bias) bv[j] += g.bias[cb + j * 32 + l31];
+        if (g.bias2) bv[j] += g.bias2[cb + j * 32 + l31];
+    }
+    auto row = [&](int b, int r) {          // scalar base of accumulator register r of block b = 2 j + i
+        return out + (size_t)(rb + (b & 1) * 32 + (r & 3) + 8 * (r >> 2)) * ldo + (cb + (b >> 1) * 32);
+    };
+    float c[2][16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) c[0][r] = row(0, r)[loff];
+#pragma unroll
+    for (int b = 0; b < 2 * NJ; ++b) {
+        if (b + 1 < 2 * NJ) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c[(b + 1) & 1][r] = row(b + 1, r)[loff];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = acc[b & 1][b >> 1][r] + bv[b >> 1];
+            v += c[b & 1][r];
+            if (relu) v = fmaxf(v, 0.f);
+            row(b, r)[loff] = v;
+        }
+    }
+}
+
 // epilogue of gemm6e for the plain / bias / bias + ReLU / accumulate / split-K-slab outputs (the host sends every other epilogue
 // - 1-bit masks, float masks, dropout - to gemm6c): one loop nest, the accumulator registers read where they are stored
 template <int NJ>
@@ -1562,6 +1603,7 @@ __device__ __forceinline__ void write_output_simple(const GemmArgs& g, const f32
     const int rb = __builtin_amdgcn_readfirstlane(rbase), cb = __builtin_amdgcn_readfirstlane(cbase);
     const int loff = 4 * hh * ldo + l31;
     const bool relu = !to_slab && (g.flags & RLT_GEMM_RELU), accum = !to_slab && (g.flags & RLT_GEMM_ACCUMULATE);
+    if (accum) { accumulate_blocks<NJ>(g, acc, out, ldo, rb, cb, loff, l31, relu); return; }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int col = cb + j * 32 + l31;
@@ -1577,7 +1619,6 @@ __device__ __forceinline__ void write_output_simple(const GemmArgs& g, const f32
                 const int dr = (r & 3) + 8 * (r >> 2);
                 float* base = out + (size_t)(rb + i * 32 + dr) * ldo + (cb + j * 32);       // scalar
                 float v = acc[i][j][r] + bv;
-                if (accum) v += base[loff];
                 if (relu) v = fmaxf(v, 0.f);
                 base[loff] = v;
             }

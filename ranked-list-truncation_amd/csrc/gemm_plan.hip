@@ -12,7 +12,7 @@
 //   RLT_GEMM6_SMALL          unset    bf16x6: set = 256 x 128 tiles everywhere (gemm6c / gemm6e / gemm6b -> gemm6)
 //   RLT_GEMM6C               1        bf16x6: 0 = gemm6b in place of gemm6c and gemm6e
 //   RLT_GEMM6E               1        bf16x6: 0 = gemm6c in place of gemm6e
-//   RLT_GEMM6E_ALL           0        bf16x6: 1 = gemm6e for A stored [M][K] below K = 1024 as well
+//   RLT_GEMM6E_ALL           0        bf16x6: 1 = gemm6e for A stored [M][K] at every K below 1024 (not only 768)
 //   RLT_GEMM6S               1        bf16x6: 0 = the tiled kernels in place of the weights-stationary one
 //   RLT_GEMM_SPLIT_KMIN      1024     split-K from this K
 //   RLT_GEMM_SPLIT_TARGET    1024     split-K: workgroups to fill (wanted slabs = target / output tiles of 128 x 128)
@@ -135,11 +135,15 @@ GemmPlan gemm_plan(const GemmCall& c) {
     // rows: 5.66 against 6.38 ms for 2048 x 256 x 1,228,800) and K >= 1024 (ffn1 dX 5.92 against 6.34 ms, ffn2 forward 5.90 against
     // 6.04) - and the epilogue is one of its plain forms; the K = 256 products (prologue / epilogue bound: 7.02 against 6.70 ms
     // for 1,228,800 x 2048 x 256) and the mask / dropout epilogues stay on gemm6c
+    // K = 768 (the attention in-projection's dX, 1,228,800 x 256 x 768, accumulated in place) runs on gemm6e as well since its
+    // accumulate epilogue reads C in batches: 2.45 against 3.21 ms accumulating, 2.29 against 2.69-2.99 plain, both layouts of B
+    // (before: 3.92 against 3.20).  K = 512 and 992 measured faster there too at that M and N (profiles/accum_epilogue_notes.md);
+    // no product of the models has those lengths, and they stay where they were
     const bool plain_epilogue = !mask && !bits_in && !bits_out && !drop;
     // the 256-wide bf16x3 tile: M % 256 == 0, N % 256 == 0, whole 32-wide K tiles, the branch-free loader preconditions
     const bool big3 = mode == 1 && !e.no_big && vec && M % 256 == 0 && N % 256 == 0 && K % 32 == 0;
     const int family = gemm6s ? RLT_GEMM_6S
-                     : pipe6 ? (e.gemm6e && plain_epilogue && (ta || K >= 1024 || e.gemm6e_all) ? RLT_GEMM_6E : RLT_GEMM_6C)
+                     : pipe6 ? (e.gemm6e && plain_epilogue && (ta || K >= 1024 || K == 768 || e.gemm6e_all) ? RLT_GEMM_6E : RLT_GEMM_6C)
                      : big6 ? RLT_GEMM_6B
                      : tile6 ? RLT_GEMM_6
                      : big3 ? RLT_GEMM_3B
