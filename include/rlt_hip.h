@@ -622,6 +622,38 @@ int rlt_attention_dropout_mask(uint32_t seed, int S, int B, int H, float p, floa
  * (tests at benchmark sizes, where the whole (S,H,B,B) mask would not fit) */
 int rlt_attention_dropout_mask_range(uint32_t seed, int pair0, int npair, int B, float p, float* out, void* stream);
 
+/* ------------------------------------------------------------------ within-list ("position-axis") attention
+ * Multi-head self-attention where every list of the mini-batch attends over its OWN S positions (nn.MultiheadAttention with
+ * batch_first=True on a (B, S, E) input: the model of the AttnCut / Choopy papers; a list's output does not depend on the
+ * other lists of the batch).  csrc/attention_seq.hip; tests: tests/test_seq_attention_abi.py, tests/test_seq_attention_gpu.py
+ * against the float64 restatement tests/seq_attention_restate.py.
+ *   qkv: (S*B, 3E) position-major as above (row s*B + b, columns [q | k | v], head h = columns h*HD..h*HD+HD of each): the
+ *   problem of (list b, head h) is rows b, b+B, .., b+(S-1)B.  scores q k^T / sqrt(HD), softmax over the keys with the row
+ *   maximum subtracted, optional dropout on the normalised probabilities, P V.
+ *   out: (S*B, E) in the same row order.  lse: (B,H,S), log of the normaliser + the row maximum, of the UNdropped scores.
+ *   drop_p, seed: the keep stream of csrc/common.h - the stream of pair b*H + h is pair_seed of (seed, b*H + h), an element is
+ *   kept iff rlt_keep of (stream, query position, key position, the rlt_drop_threshold of drop_p), kept weights are scaled by
+ *   1.f / (1.f - drop_p); the backward recomputes the same mask from (drop_p, seed).
+ *   bwd: ONE launch writes the dQ, dK and dV columns of dqkv (S*B, 3E) and nothing else: a whole S x S problem lives in one
+ *   workgroup, so no sum crosses workgroups - delta = rowsum(dout * out) is formed in the kernel, no atomics, no allocation,
+ *   no host synchronisation, two calls give the same bits.  rlt_seq_attention_bwd_workspace is 0 today (ws may be NULL).
+ * HD in {16, 64}; 1 <= S <= 1024; any B, H >= 1 with S*B*3E < 2^40 elements (the kernels index in 64 bits) and
+ * B * ceil(H * HD / 64) < 2^24 workgroups.  The three precision codes run the SAME exact-fp32 kernels (32x32x2 f32 MFMA, fp32
+ * accumulation, fp32 exp): at 4*B*H*S*S*HD flops per product pass that is at least what BF16X6 and BF16X3 promise; `precision`
+ * is validated like everywhere else.
+ * Errors before any launch, in this order: RLT_E_ARG (a precision code outside the three + DEFAULT - workspace query: 0 bytes;
+ * a NULL qkv / out / dout / lse / dqkv; non-positive S / B / H; drop_p outside [0, 1)), RLT_E_SHAPE (HD not 16 or 64, S > 1024,
+ * the index limits above), RLT_E_ALIGN (a pointer off 16 bytes), RLT_E_WORKSPACE (ws_bytes below the query's answer).
+ * Algorithmic bytes: fwd reads 12*S*B*E (qkv) and writes 4*S*B*E + 4*B*H*S; bwd reads 12*S*B*E + 8*S*B*E + 4*B*H*S and writes
+ * 12*S*B*E (K / V - in the backward also Q / dO - tiles are re-read once per 128 owned rows at head dim 64, per 32 at head
+ * dim 16, from L2). */
+size_t rlt_seq_attention_bwd_workspace(int S, int B, int H, int HD, float drop_p, int precision);   /* may be 0 */
+int rlt_seq_attention_fwd(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed,
+                          float* out, float* lse, int precision, void* stream);
+int rlt_seq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
+                          int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv,
+                          void* ws, size_t ws_bytes, int precision, void* stream);
+
 /* ------------------------------------------------------------------ BiLSTM recurrence (M2)
  * One bidirectional LSTM layer with hidden size 128 (nn.LSTM(..., hidden_size=128,
  * bidirectional=True, batch_first=True), models/AttnCut.py:8): gate order i,f,g,o, h0=c0=0.

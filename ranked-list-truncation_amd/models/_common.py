@@ -66,13 +66,20 @@ def bilstm(x_pm, params, S, B):
     return ops.bilstm(x_pm, params, S, B)
 
 
-def encoder(x_pm, params, n_head, S, B, drop_p=0.0):
-    """Stack of post-norm encoder layers with list-axis attention.  drop_p > 0 applies the four
-    dropouts of nn.TransformerEncoderLayer: attention probabilities, dropout1 (attention branch),
+def check_attention_axis(axis):
+    """'list' (the lists of a mini-batch attend to each other at every position: what the reference computes) or 'position'
+    (every list attends over its own positions: the model of the papers); anything else is a ValueError.  Parameters,
+    state_dict keys, shapes and initialisation do not depend on it."""
+    return ops.check_attention_axis(axis)
+
+
+def encoder(x_pm, params, n_head, S, B, drop_p=0.0, axis="list"):
+    """Stack of post-norm encoder layers with list-axis (axis='list') or within-list (axis='position') attention.  drop_p > 0
+    applies the four dropouts of nn.TransformerEncoderLayer: attention probabilities, dropout1 (attention branch),
     the FFN hidden dropout and dropout2 (FFN branch)."""
     h = x_pm
     for layer in params.layers.children():
-        h = ops.encoder_layer(h, layer, S, B, n_head, drop_p)
+        h = ops.encoder_layer(h, layer, S, B, n_head, drop_p, axis=axis)
     return h
 
 

@@ -103,6 +103,10 @@ _SIGNATURES = {
     "rlt_list_attention_bwd_dkv": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
     "rlt_list_attention_bwd_dq": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
     "rlt_list_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
+    # within-list ("position-axis") attention (csrc/attention_seq.hip)
+    "rlt_seq_attention_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_float, c_int]),
+    "rlt_seq_attention_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_int, P]),
+    "rlt_seq_attention_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_size_t, c_int, P]),
     "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),

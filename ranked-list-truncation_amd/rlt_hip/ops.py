@@ -308,6 +308,54 @@ def list_attention(qkv, S, B, H, drop_p=0.0):
     return ListAttentionFn.apply(qkv, S, B, H, drop_p, next_seed() if drop_p > 0 else 0)
 
 
+# ------------------------------------------------------------------------------ within-list ("position-axis") attention
+def _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr):
+    out = _empty((S * B, H * HD), qkv)
+    lse = _empty((B, H, S), qkv)
+    _launch("seq_attn_fwd", lambda: call("rlt_seq_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, seed, ptr(out), ptr(lse), pr, stream()))
+    return out, lse
+
+
+def _seq_attention_bwd(qkv, out, dout, lse, S, B, H, HD, drop_p, seed, pr):
+    dqkv = torch.empty_like(qkv)
+    ws_bytes = query("rlt_seq_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
+    ws = workspace(ws_bytes, qkv.device) if ws_bytes else None
+    _launch("seq_attn_bwd", lambda: call("rlt_seq_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, seed,
+                                         ptr(dqkv), ptr(ws), ws_bytes, pr, stream()))
+    return dqkv
+
+
+class SeqAttentionFn(Function):
+    """qkv (S*B, 3E) -> concatenated heads (S*B, E); every list attends over its own S positions (rlt_seq_attention_*: one
+    launch forward, one launch backward)."""
+
+    @staticmethod
+    def forward(ctx, qkv, S, B, H, drop_p=0.0, seed=0):
+        E = qkv.shape[1] // 3
+        if qkv.shape != (S * B, 3 * E) or E % H:
+            raise RuntimeError(f"seq_attention: qkv {tuple(qkv.shape)} does not match S*B = {S * B} rows of 3 * H * HD columns")
+        HD = E // H
+        ctx.prec = pr = current_precision()
+        out, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr)
+        ctx.dims = (S, B, H, HD)
+        ctx.drop = (drop_p, seed)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        S, B, H, HD = ctx.dims
+        drop_p, seed = ctx.drop
+        dqkv = _seq_attention_bwd(qkv, out, N.f32c(dout), lse, S, B, H, HD, drop_p, seed, ctx.prec)
+        return dqkv, None, None, None, None, None
+
+
+def seq_attention(qkv, S, B, H, drop_p=0.0):
+    N.require_cuda(qkv)
+    return SeqAttentionFn.apply(N.f32c(qkv), S, B, H, drop_p, next_seed() if drop_p > 0 else 0)
+
+
 # ------------------------------------------------------------------------------ whole encoder layer
 class EncoderLayerFn(Function):
     """One post-norm nn.TransformerEncoderLayer (list-axis attention, ReLU FFN) as ONE tape node on the path-level
@@ -372,6 +420,7 @@ class EncoderLayerKernelsFn(Function):
     @staticmethod
     def forward(ctx, *args):
         ctx.prec = current_precision()
+        ctx.axis = "list"
         with precision(ctx.prec):          # every gemm() below reads the scope
             return EncoderLayerKernelsFn._forward(ctx, *args)
 
@@ -389,14 +438,18 @@ class EncoderLayerKernelsFn(Function):
         s_attn, s_ln1, s_ffn, s_ln2 = seeds
         qkv = _empty((T, 3 * E), x)
         gemm(0, 1, T, 3 * E, E, x, E, in_w, E, qkv, 3 * E, bias=in_b)
-        att = _empty((T, E), x)
-        lse = _empty((S, H, B), x)
-        img_bytes = query("rlt_list_attention_fwd_workspace", S, B, H, HD, drop_p, pr)
-        images = workspace(img_bytes, x.device) if img_bytes else None
-        _launch("attn_fwd", lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, s_attn,
-                                         ptr(att), ptr(lse), ptr(images), img_bytes, pr, stream()))
-        if images is not None and not N.load().rlt_list_attention_images_retained(S, B, H, HD, pr):
-            images = None                                    # scratch of the forward call: not kept for the backward
+        images = None
+        if ctx.axis == "position":
+            att, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, s_attn, pr)
+        else:
+            att = _empty((T, E), x)
+            lse = _empty((S, H, B), x)
+            img_bytes = query("rlt_list_attention_fwd_workspace", S, B, H, HD, drop_p, pr)
+            images = workspace(img_bytes, x.device) if img_bytes else None
+            _launch("attn_fwd", lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, s_attn,
+                                             ptr(att), ptr(lse), ptr(images), img_bytes, pr, stream()))
+            if images is not None and not N.load().rlt_list_attention_images_retained(S, B, H, HD, pr):
+                images = None                                    # scratch of the forward call: not kept for the backward
         proj = _empty((T, E), x)
         gemm(0, 1, T, E, E, att, E, out_w, E, proj, E, bias=out_b)
         h1 = _empty((T, E), x)
@@ -463,16 +516,19 @@ class EncoderLayerKernelsFn(Function):
         datt = _empty((T, E), x)
         gemm(0, 0, T, E, E, dr1, E, out_w, E, datt, E)
         # attention
-        images = ctx.images
-        dqkv = torch.empty_like(qkv)
-        ws_bytes = query("rlt_list_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
-        ws = workspace(ws_bytes, x.device)
-        call("rlt_list_attention_bwd_prepare", ptr(att), ptr(datt), ptr(lse), S, B, H, HD, drop_p, ptr(images), ptr(ws), ws_bytes, pr, stream())
-        _launch("attn_bwd_dkv", lambda: call("rlt_list_attention_bwd_dkv", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                             S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
-        _launch("attn_bwd_dq", lambda: call("rlt_list_attention_bwd_dq", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                            S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
-        ctx.images = None
+        if ctx.axis == "position":
+            dqkv = _seq_attention_bwd(qkv, att, datt, lse, S, B, H, HD, drop_p, s_attn, pr)
+        else:
+            images = ctx.images
+            dqkv = torch.empty_like(qkv)
+            ws_bytes = query("rlt_list_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
+            ws = workspace(ws_bytes, x.device)
+            call("rlt_list_attention_bwd_prepare", ptr(att), ptr(datt), ptr(lse), S, B, H, HD, drop_p, ptr(images), ptr(ws), ws_bytes, pr, stream())
+            _launch("attn_bwd_dkv", lambda: call("rlt_list_attention_bwd_dkv", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
+                                                 S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
+            _launch("attn_bwd_dq", lambda: call("rlt_list_attention_bwd_dq", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
+                                                S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
+            ctx.images = None
         # in_proj
         dw_in, db_in = _empty((3 * E, E), x), _empty((3 * E,), x)
         gemm(1, 0, 3 * E, E, T, dqkv, 3 * E, x, E, dw_in, E, colsum_a=db_in)
@@ -481,11 +537,44 @@ class EncoderLayerKernelsFn(Function):
                 None, None, None, None, None, None)
 
 
-def encoder_layer(x, layer, S, B, H, drop_p=0.0, eps=1e-5):
-    """`layer`: a ParamTree mirror of nn.TransformerEncoderLayer."""
+class EncoderLayerSeqFn(Function):
+    """The encoder layer with WITHIN-LIST attention (every list attends over its own positions; nn.TransformerEncoderLayer with
+    batch_first=True): the host composition of EncoderLayerKernelsFn - in_proj, attention, out_proj, the two residual +
+    LayerNorm calls, the FFN pair with its 1-bit mask, the two RLT_GEMM_ACCUMULATE fan-out gradients - with
+    rlt_seq_attention_fwd / _bwd in the attention slot.  This IS the product path of axis='position'."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.prec = current_precision()
+        ctx.axis = "position"
+        with precision(ctx.prec):
+            return EncoderLayerKernelsFn._forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, dy):
+        with precision(ctx.prec):
+            return EncoderLayerKernelsFn._backward(ctx, dy)
+
+
+ATTENTION_AXES = ("list", "position")
+
+
+def check_attention_axis(axis):
+    if axis not in ATTENTION_AXES:
+        raise ValueError(f"attention axis must be one of {ATTENTION_AXES}, got {axis!r}")
+    return axis
+
+
+def encoder_layer(x, layer, S, B, H, drop_p=0.0, eps=1e-5, axis="list"):
+    """`layer`: a ParamTree mirror of nn.TransformerEncoderLayer.  axis='list': the lists of the mini-batch attend to each other at
+    every position (what the reference computes); axis='position': every list attends over its own positions."""
+    check_attention_axis(axis)
     att = layer.self_attn
     seeds = tuple(next_seed() for _ in range(4)) if drop_p > 0 else (0, 0, 0, 0)
-    fn = EncoderLayerKernelsFn if (KernelTimer.active is not None or KERNEL_LEVEL_ENCODER[0]) else EncoderLayerFn
+    if axis == "position":
+        fn = EncoderLayerSeqFn
+    else:
+        fn = EncoderLayerKernelsFn if (KernelTimer.active is not None or KERNEL_LEVEL_ENCODER[0]) else EncoderLayerFn
     return fn.apply(x, att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias,
                                 layer.norm1.weight, layer.norm1.bias, layer.linear1.weight, layer.linear1.bias,
                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias,

@@ -89,6 +89,8 @@ class ScalarLog:
 
 
 class Trainer:
+    attention_axis = "list"      # of a trainer a driver assembles by hand (verify_probe.py); __init__ sets the run's
+
     def __init__(self, args):
         self.args = args
         self.seq_len = 300 if args.retrieve_data == 'robust04' else 40
@@ -146,33 +148,37 @@ class Trainer:
             raise ValueError(f"{name} is built for ONE list length; the data holds train lengths {data.lengths} and test "
                              f"lengths {data.test_lengths} (only the BiLSTM models bicut / attncut / mtattncut take "
                              "length-bucketed batches)")
+        # --attention-axis: 'list' (the reference: lists attend to each other) or 'position' (every list over its own positions);
+        # the weights do not depend on it, so it is recorded beside them and a mismatch on loading is a warning, not an error
+        self.attention_axis = axis = getattr(args, "attention_axis", "list")
         if name == 'bicut':                                                    # run.py:59-64
             self.model = BiCut(input_size=feat, dropout=args.dropout, sparse_input=self.sparse_bicut)
             self.criterion = losses.BiCutLoss(metric=args.criterion)
         elif name == 'choopy':                                                 # run.py:65-68
-            self.model = Choopy(seq_len=self.seq_len, dropout=args.dropout)
+            self.model = Choopy(seq_len=self.seq_len, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.ChoopyLoss(metric=args.criterion)
         elif name == 'attncut':                                                # run.py:69-75
-            self.model = AttnCut(input_size=feat, dropout=args.dropout)
+            self.model = AttnCut(input_size=feat, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.DivLoss(metric=args.criterion, div_type=args.div_type,
                                             augmented=args.augmented_reward)
         elif name == 'mtchoopy':                                               # run.py:76-79
-            self.model = MtChoopy(seq_len=self.seq_len, num_tasks=args.num_tasks, dropout=args.dropout)
+            self.model = MtChoopy(seq_len=self.seq_len, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
                                               classi_weight=args.class_weight, num_tasks=args.num_tasks)
         elif name == 'mtattncut':                                              # run.py:80-84
-            self.model = MtAttnCut(input_size=feat, num_tasks=args.num_tasks, dropout=args.dropout)
+            self.model = MtAttnCut(input_size=feat, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
                                               classi_weight=args.class_weight, num_tasks=args.num_tasks)
         elif name == 'mmoecut':                                                # run.py:85-90 (num_experts exposed)
             self.model = MMOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat,
-                                 dropout=args.dropout, num_experts=args.num_experts)
+                                 dropout=args.dropout, num_experts=args.num_experts, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
         elif name == 'moecut':                                                 # run.py:91-96
-            self.model = MOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat, dropout=args.dropout)
+            self.model = MOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat, dropout=args.dropout,
+                                attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
         elif name == 'mtple':                                                  # run.py:97-102
-            self.model = PLECut(seq_len=self.seq_len, input_size=feat, dropout=args.dropout, num_experts=3)
+            self.model = PLECut(seq_len=self.seq_len, input_size=feat, dropout=args.dropout, num_experts=3, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
         else:
             raise ValueError(f"model {name!r} is outside the HIP hot path "
@@ -184,6 +190,7 @@ class Trainer:
         self.flat = FlatModel(self.model)
         self.flat.broadcast_params()
         if resume:
+            self._warn_axis(resume.get("attention_axis", "list"), args.resume)
             self.model.load_state_dict(resume["model"])         # in place: into the views of the flat bucket
         total_steps = max(1, args.epochs * len(self.train_loader))
         self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **grad_guard_kwargs(args),   # run.py:104
@@ -320,8 +327,15 @@ class Trainer:
             self.best_test_dcg = dcg
         return loss, f1, dcg
 
+    def _warn_axis(self, stored, path):
+        if stored != self.attention_axis:
+            logging.warning('{} was written with --attention-axis {}; this run uses {} (the weights load, the model differs)'.format(
+                path, stored, self.attention_axis))
+
     def save_model(self):
         os.makedirs(self.save_path, exist_ok=True)
+        with open(os.path.join(self.save_path, '{}.pkl.meta.json'.format(self.model_name)), "w") as f:      # beside the state_dict
+            json.dump({"attention_axis": self.attention_axis}, f)
         # clone: parameters are views of the flat bucket
         state = {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}
         torch.save(state, os.path.join(self.save_path, '{}.pkl'.format(self.model_name)))
@@ -333,11 +347,16 @@ class Trainer:
         opt = {k: (v.detach().clone().cpu() if torch.is_tensor(v) else v) for k, v in self.optimizer.state_dict().items()}
         state = {"model": {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}, "optimizer": opt, "epoch": epoch,
                  "best_test_f1": self.best_test_f1, "best_test_dcg": self.best_test_dcg, "best_epoch": self.best_epoch,
-                 "f1_record": self.f1_record, "dcg_record": self.dcg_record, "history": self.history}
+                 "f1_record": self.f1_record, "dcg_record": self.dcg_record, "history": self.history,
+                 "attention_axis": self.attention_axis}
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         torch.save(state, path)
 
     def load_model(self):
+        meta = self.model_path + '.meta.json'
+        if os.path.exists(meta):
+            with open(meta) as f:
+                self._warn_axis(json.load(f).get("attention_axis", "list"), self.model_path)
         self.model.load_state_dict(torch.load(self.model_path, map_location=self.device))
         logging.info('The best model has beed loaded from {}\n'.format(self.model_path))
 
@@ -461,6 +480,7 @@ class Trainer:
                     self.writer.add_scalar('report/{}'.format(key), v, L)
         if spec is not None:                    # the reward the reward columns are in: compare_reports(metric='reward') checks it
             per_len["reward_spec"] = np.asarray(eval_reward_text(spec))
+        per_len["attention_axis"] = np.asarray(self.attention_axis)
         np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
                  summary=np.asarray(json.dumps(summaries)), **{k: np.concatenate(v) for k, v in arrays.items()}, **per_len)
         return summaries
@@ -687,6 +707,10 @@ def build_parser():
     p.add_argument('--synthetic', type=int, default=0, help="write a robust04-shaped synthetic set into --dataset-base first")
     p.add_argument('--use-conf', type=int, default=1, help="override lr/batch/dropout/wd/task weights from hyper_parameter_<dataset>.conf")
     p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--attention-axis', type=str, default='list', choices=('list', 'position'),
+                   help="axis the encoder layers attend over: 'list' = the lists of a mini-batch attend to each other at every position "
+                        "(the reference); 'position' = every list attends over its own positions (the papers' model; a list's cut "
+                        "then does not depend on its batch).  Recorded in --history-json, --report-out and --save-state")
     p.add_argument('--history-json', type=str, default=None, help="rank 0 writes the per-epoch train / test means and the best / best-5 figures here")
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "
@@ -797,7 +821,7 @@ def main(argv=None):
             fin = lambda v: v if v is not None and math.isfinite(v) else None     # -inf (no test epoch) is not valid JSON
             json.dump({"history": trainer.history, "best_f1": fin(trainer.best_test_f1), "best_dcg": fin(trainer.best_test_dcg),
                        "best5_f1": fin(trainer.best5_f1), "best5_dcg": fin(trainer.best5_dcg), "best_epoch": trainer.best_epoch,
-                       "world": trainer.world, **({"baselines": trainer.baseline_results} if args.baselines else {}),
+                       "world": trainer.world, "attention_axis": trainer.attention_axis, **({"baselines": trainer.baseline_results} if args.baselines else {}),
                        **({"eval_reward": {"spec": eval_reward_text(eval_reward_spec(args)),
                                            "report": getattr(trainer, "report_results", None),
                                            "cut_sweep": getattr(trainer, "sweep_results", None)}} if eval_reward_spec(args) else {})}, f)

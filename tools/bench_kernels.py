@@ -1218,6 +1218,97 @@ def reward_eval(shapes=((1048576, 300),), cuts=(1, 19), reps=9):
             torch.cuda.empty_cache()
 
 
+def seq_attention(shapes=((4096, 300, 4, 64), (8192, 300, 8, 16)), reps=7, runs=2, layer=True):
+    """Within-list attention (rlt_seq_attention_fwd / _bwd) at (B, S, H, HD): the median of `reps` HIP-event timings in each of `runs`
+    separate runs, TFLOP/s of the algorithm's flops (4*B*H*S*S*HD forward, 2.5 x that backward: five products) against the 157.3
+    TFLOP/s f32-MFMA peak; against the composition a user would otherwise write in torch (permute to (B, H, S, HD), fp32
+    scaled_dot_product_attention - matmul / softmax / matmul if it refuses fp32 - and permute back, autograd backward; the permutes
+    counted); the list-axis launches at the same shape for context; and the encoder-layer step (forward + backward) per axis."""
+    import statistics
+    PEAK = 157.3
+
+    def median_ms(fn):
+        fn()                                                     # warm-up: code objects, allocator
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return statistics.median(ts)
+
+    for B, S, H, HD in shapes:
+        E, T = H * HD, S * B
+        gf = 4.0 * B * H * S * S * HD / 1e9
+        qkv = torch.randn(T, 3 * E, device=dev)
+        dout = torch.randn(T, E, device=dev)
+        out, lse, dqkv = torch.empty(T, E, device=dev), torch.empty(B, H, S, device=dev), torch.empty_like(qkv)
+        D = N.PRECISION_DEFAULT
+        fwd = lambda: call("rlt_seq_attention_fwd", ptr(qkv), S, B, H, HD, 0.0, 0, ptr(out), ptr(lse), D, stream())
+        bwd = lambda: call("rlt_seq_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, 0.0, 0, ptr(dqkv), None, 0, D, stream())
+
+        x = qkv.detach().clone().requires_grad_(True)
+
+        def torch_fwd():
+            q, k, v = x.view(S, B, 3, H, HD).permute(2, 1, 3, 0, 4)
+            try:
+                o = torch.nn.functional.scaled_dot_product_attention(q, k, v)
+            except RuntimeError:
+                o = torch.softmax(q @ k.transpose(-1, -2) / HD ** 0.5, -1) @ v
+            return o.permute(2, 0, 1, 3).reshape(T, E)
+
+        def torch_both():
+            x.grad = None
+            torch_fwd().backward(dout)
+
+        def torch_fwd_only():
+            with torch.no_grad():
+                torch_fwd()
+
+        o_t = torch_fwd().detach()
+        fwd()
+        torch.cuda.synchronize()
+        print(f"seq_attention B{B} S{S} H{H} HD{HD}: max |out - torch| = {float((out - o_t).abs().max()):.2e}", flush=True)
+        for r in range(runs):
+            f, b = median_ms(fwd), median_ms(bwd)
+            tf, tb = median_ms(torch_fwd_only), median_ms(torch_both)
+            print(f"  run {r}: rlt fwd {f:8.3f} ms {gf / f:6.1f} TF/s ({100 * gf / f / PEAK:4.1f} % of peak) | bwd {b:8.3f} ms "
+                  f"{2.5 * gf / b:6.1f} TF/s ({100 * 2.5 * gf / b / PEAK:4.1f} %) | fwd+bwd {f + b:8.3f} ms", flush=True)
+            print(f"  run {r}: torch composition fwd {tf:8.3f} ms | fwd+bwd {tb:8.3f} ms | rlt / torch: fwd {f / tf:5.2f}, fwd+bwd {(f + b) / tb:5.2f}"
+                  + ("  (SLOWER than the torch composition here)" if f + b > tb else ""), flush=True)
+        del x, o_t
+        torch.cuda.empty_cache()
+        # context: the list-axis launches at the same shape (4*S*H*B*B*HD flops per product pass: B / S times the work)
+        lse_l = torch.empty(S, H, B, device=dev)
+        ib = N.query("rlt_list_attention_fwd_workspace", S, B, H, HD, 0.0, D)
+        images = torch.empty(max(ib, 16) // 4, device=dev) if ib else None
+        wb = N.query("rlt_list_attention_bwd_workspace", S, B, H, HD, 0.0, D)
+        ws = torch.empty(wb // 4 + 4, device=dev)
+        lf = median_ms(lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, 0.0, 0, ptr(out), ptr(lse_l), ptr(images), ib, D, stream()))
+        lb = median_ms(lambda: call("rlt_list_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse_l), S, B, H, HD, 0.0, 0, ptr(images),
+                                    ptr(dqkv), ptr(ws), wb, D, stream()))
+        print(f"  context: list-axis launches at the same shape: fwd {lf:8.3f} ms | bwd {lb:8.3f} ms", flush=True)
+        del images, ws, qkv, dout, out, dqkv
+        torch.cuda.empty_cache()
+        if layer:
+            from models._common import ParamTree
+            lay = ParamTree(torch.nn.TransformerEncoderLayer(E, H, dropout=0.0)).to(dev)
+            h = torch.randn(T, E, device=dev, requires_grad=True)
+            g = torch.randn(T, E, device=dev)
+            for axis in ("list", "position"):
+                def step():
+                    h.grad = None
+                    for p in lay.parameters():
+                        p.grad = None
+                    ops.encoder_layer(h, lay, S, B, H, axis=axis).backward(g)
+                print(f"  encoder layer step (fwd + bwd), axis={axis}: {median_ms(step):8.3f} ms", flush=True)
+            del lay, h, g
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
