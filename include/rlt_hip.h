@@ -40,7 +40,8 @@ int rlt_abi_version(void);
 /* Precision of the MFMA contractions (the rlt_gemm* family, rlt_list_attention_*, the BiLSTM recurrences); inputs, outputs,
  * softmax, LayerNorm, gate nonlinearities, losses and every accumulator are fp32 in all modes.
  *   RLT_PRECISION_FP32   exact fp32 products on the f32 MFMA (157 TFLOP/s peak) - bit-for-bit fp32 fma chains
- *   RLT_PRECISION_BF16X6 fp32-FAITHFUL products on the bf16 MFMA: every operand split exactly into three bf16 values
+ *   RLT_PRECISION_BF16X6 fp32-FAITHFUL products on the bf16 MFMA (the split and the order of the products are implemented
+ *                        once, in csrc/split6.h): every operand split exactly into three bf16 values
  *                        (8 + 8 + 8 significand bits: all 24 operand bits enter), six of the nine partial products kept,
  *                        each exact in the matrix pipe, fp32 accumulation; what is dropped is < 2^-23 of the product
  *                        in the worst case (under one fp32 ulp; 2^-29 typical).  Held to the FP32 mode's tolerances in

@@ -20,25 +20,14 @@
 
 namespace {
 
-#ifndef RLT_A16_T
-#define RLT_A16_T 64
-#endif
-#ifndef RLT_A16_NS
-#define RLT_A16_NS 2
-#endif
-#ifndef RLT_A16_OCC
-#define RLT_A16_OCC 4
-#endif
-#ifndef RLT_A16_PRIO
-#define RLT_A16_PRIO 1
-#endif
-// matrix bursts run at raised wave priority (see the forward kernel)
-#define PRIO_MFMA() do { if (RLT_A16_PRIO) __builtin_amdgcn_s_setprio(RLT_A16_PRIO); } while (0)
-#define PRIO_VALU() do { if (RLT_A16_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-constexpr int T16 = RLT_A16_T;     // rows per LDS tile
+constexpr int OCC16 = 4;           // wavefronts per SIMD the register budget is declared for
+constexpr int PRIO16 = 1;          // wave priority of the matrix bursts (see the forward kernel); 0: never raised
+#define PRIO_MFMA() __builtin_amdgcn_s_setprio(PRIO16)
+#define PRIO_VALU() __builtin_amdgcn_s_setprio(0)
+constexpr int T16 = 64;            // rows per LDS tile
 constexpr int LDR = 20;            // row-major copy: floats per row (16 + 4: conflict-free b128 reads at row stride 20)
 constexpr int LDT = T16 + 4;       // transposed copy: floats per d row
-constexpr int NS = RLT_A16_NS;     // 16-row sub-tiles owned by a wavefront
+constexpr int NS = 2;              // 16-row sub-tiles owned by a wavefront
 constexpr int NT = T16 / 16;       // 16-row sub-tiles per LDS tile
 constexpr int WROWS = NS * 16;     // rows owned by a wavefront
 constexpr int GROWS = 4 * WROWS;   // ... by a workgroup
@@ -115,7 +104,7 @@ __device__ __forceinline__ float col_sum(float v) {
 
 // ------------------------------------------------------------------------------------------ forward
 template <bool DROP>
-__global__ __launch_bounds__(256, RLT_A16_OCC) void attn16_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, OCC16) void attn16_fwd_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float Ks[2][T16 * LDR];      // K, row-major
     __shared__ __attribute__((aligned(16))) float Vt[2][16 * LDT];       // V, transposed
     __shared__ __attribute__((aligned(16))) uint32_t Hc[2][T16];         // dropout: column (key) hashes of the tile
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(256, RLT_A16_OCC) void attn16_fwd_kernel(AttnArgs a
 
 // ------------------------------------------------------------------------------------------ dQ
 template <bool DROP>
-__global__ __launch_bounds__(256, RLT_A16_OCC) void attn16_bwd_dq_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, OCC16) void attn16_bwd_dq_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float Ks[2][T16 * LDR];      // K, row-major (scores)
     __shared__ __attribute__((aligned(16))) float Kt[2][16 * LDT];       // K, transposed (dQ)
     __shared__ __attribute__((aligned(16))) float Vs[2][T16 * LDR];      // V, row-major (dP)
@@ -382,7 +371,7 @@ __global__ __launch_bounds__(256, RLT_A16_OCC) void attn16_bwd_dq_kernel(AttnArg
 
 // ------------------------------------------------------------------------------------------ dK, dV
 template <bool DROP>
-__global__ __launch_bounds__(256, RLT_A16_OCC) void attn16_bwd_dkv_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, OCC16) void attn16_bwd_dkv_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float Qs[2][T16 * LDR];      // Q row-major (scores), transposed (dK)
     __shared__ __attribute__((aligned(16))) float Qt[2][16 * LDT];
     __shared__ __attribute__((aligned(16))) float Ds[2][T16 * LDR];      // dO row-major (dP), transposed (dV)

@@ -14,103 +14,21 @@
 //  * fp32 -> (hi, lo) splitting happens once per workgroup per tile, at staging time (4x4 register transpose
 //    for the transposed image), not per MFMA.
 #include "attention_common.h"
+#include "split6.h"
 
 #include <stdlib.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef RLT_ASM_DMA
-#define RLT_ASM_DMA 1         // head dim 64: LDS-DMA issued as inline assembly (see dma_copy)
-#endif
-#ifndef RLT_ASM_DMA_HD16
-#define RLT_ASM_DMA_HD16 0    // also at head dims 16 / 32
-#endif
-#ifndef RLT_SPREAD_HD16
-#define RLT_SPREAD_HD16 0     // head dims 16 / 32 (needs RLT_ASM_DMA_HD16): dQ and dK+dV kernels spread the pieces over the tile body
-#endif
-#ifndef RLT_FWD_TRV
-#define RLT_FWD_TRV 1         // forward kernel, head dim 64: V^T by transposed reads from the V rows image (no transposed image of V)
-#endif
-#ifndef RLT_DQ_STEPPED
-#define RLT_DQ_STEPPED 1      // dQ kernel, head dim 64, no dropout: stepped tile body
-#endif
-#ifndef RLT_DQ_TRREAD
-#define RLT_DQ_TRREAD 1       // ... with K^T read transposed from the K rows image (K^T image not copied)
-#endif
-#ifndef RLT_DQ_SPREAD_EVERY
-#define RLT_DQ_SPREAD_EVERY 4 // ... one LDS-DMA piece every so many of its 24 matrix steps (5 pieces per wavefront)
-#endif
-#ifndef RLT_DKV_TRREAD
-#define RLT_DKV_TRREAD 1      // stepped dK+dV body: transposed operands by ds_read_b64_tr_b16 from the rows images (no transposed images copied)
-#endif
-#ifndef RLT_STEPPED_SPREAD
-#define RLT_STEPPED_SPREAD 1  // stepped tile body: LDS-DMA pieces of the next tile spread over the matrix steps
-#endif
-#ifndef RLT_FWD_SPREAD
-#define RLT_FWD_SPREAD 0      // forward kernel, head dim 64: LDS-DMA pieces spread over the tile body (measured +2 %: off)
-#endif
-#ifndef RLT_DQ_SPREAD
-#define RLT_DQ_SPREAD 1       // dQ kernel likewise (measured -2 %)
-#endif
-#ifndef RLT_SPREAD_EVERY
-#define RLT_SPREAD_EVERY 6    // one piece every so many matrix steps (5 pieces per wavefront and tile with RLT_DKV_TRREAD, 32 steps)
-#endif
-#ifndef RLT_STEPPED
-#define RLT_STEPPED 1         // dK+dV, head dim 64: stepped tile body with this fragment prefetch distance (matrix steps; 1 measured best: 4.63 vs 4.69 ms at 2); 0 = compiler-scheduled body
-#endif
-#ifndef RLT_HD16_SMALL_MFMA
-#define RLT_HD16_SMALL_MFMA 1        // head dim 16: dV / dK products on v_mfma_f32_16x16x32_bf16 (0: the padded 32x32x16 form)
-#endif
+constexpr int DQ_SPREAD_EVERY = 4;       // stepped dQ body: one LDS-DMA piece every so many of its 24 matrix steps (5 pieces per wavefront)
+constexpr int SPREAD_EVERY = 6;          // stepped dK+dV body: one piece every so many of its 32 matrix steps (5 pieces per wavefront and tile)
+constexpr int PREFETCH = 1;              // stepped dK+dV body: fragment prefetch distance in matrix steps (1 measured best: 4.63 vs 4.69 ms at 2)
 constexpr float LAZY_TH = 8.f;           // forward: the running-maximum reference moves when a tile exceeds it by > 2^8
 constexpr int LDT3 = 72;                 // bf16 elements per row of a transposed [d][64 rows] image (144 B)
 // rows of a transposed image: the HD rows of the tile, plus - where the 32-row MFMA operand has rows to spare (head
 // dim 16) - one row of ones: the product that forms O^T = V^T P^T then also delivers sum_k P[k][q] in its row HD, i.e.
 // the softmax normaliser, and the forward kernel keeps no running sum of its own (32 adds per 64 keys less)
 template <int HD> constexpr int T_rows() { return HD < 32 ? HD + 1 : HD; }
-
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ void split4(float a, float b, float c, float d, uint2& hi, uint2& lo) {
-    hi.x = pk2(a, b);
-    hi.y = pk2(c, d);
-    // opaque to the optimiser: otherwise hipcc re-derives the low element's bf16 with a second v_cvt_pk (x, 0) instead
-    // of shifting the packed pair (one extra VALU instruction per two elements)
-    asm("" : "+v"(hi.x), "+v"(hi.y));
-    lo.x = pk2(a - __builtin_bit_cast(float, hi.x << 16), b - __builtin_bit_cast(float, hi.x & 0xffff0000u));
-    lo.y = pk2(c - __builtin_bit_cast(float, hi.y << 16), d - __builtin_bit_cast(float, hi.y & 0xffff0000u));
-}
-__device__ __forceinline__ bf16x8 as_frag(uint4 v) { return __builtin_bit_cast(bf16x8, v); }
-// ds_read_b64_tr_b16: per 16-lane group a 4-row x 16-column block of 16-bit elements, delivered column-major (lane i of the
-// group gets column i of the 4 rows); every lane's address 8-byte aligned, EXEC all ones (cdna_hip_programming.md T10)
-typedef short v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4s tr_read(const uint16_t* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(p));
-}
-__device__ __forceinline__ bf16x8 cat_frag(v4s a, v4s b) {
-    typedef short v8s __attribute__((ext_vector_type(8)));
-    const v8s v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-// 8 fp32 -> hi / lo bf16x8 fragments
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-    uint2 h0, l0, h1, l1;
-    split4(x[0], x[1], x[2], x[3], h0, l0);
-    split4(x[4], x[5], x[6], x[7], h1, l1);
-    hi = as_frag(make_uint4(h0.x, h0.y, h1.x, h1.y));
-    lo = as_frag(make_uint4(l0.x, l0.y, l1.x, l1.y));
-}
-
-__device__ __forceinline__ f32x16 mfma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-    return c;
-}
 
 // position of row `key` (0..63) inside a transposed image row: 16-blocks keep their place, inside a block
 // bits 2 and 3 are swapped (so that accumulator registers 8s..8s+7 of lane-half h are 8 consecutive slots)
@@ -322,8 +240,8 @@ constexpr int QT3 = 256;                  // rows owned by a workgroup of the sp
 // body, i.e. wait there for the NEXT tile's copy.  The copy of tile t+1 goes to the other stage, so the only ordering
 // needed is dma_wait_barrier<true>() before that stage is read.  Measured at head dim 64 (r02_notes.md): dK+dV kernel -2 %,
 // forward kernel -1.5 %, dQ kernel -1 % (with frags_ready() below; without it the forward kernel got 5 % slower).
-template <int HD> constexpr bool asm_dma() { return RLT_ASM_DMA != 0 && (HD == 64 || RLT_ASM_DMA_HD16 != 0); }
-template <int HD> constexpr bool spread_dma() { return asm_dma<HD>() && (HD == 64 || RLT_SPREAD_HD16 != 0); }
+// Head dim 64 only; there the dQ and the stepped dK+dV bodies also spread the pieces of the next tile over their matrix steps.
+template <int HD> constexpr bool asm_dma() { return HD == 64; }
 
 template <int NBYTES, bool ASM = false>
 __device__ __forceinline__ void dma_copy(uint8_t* lds_dst, const uint8_t* __restrict__ gsrc, int wv, int lane) {
@@ -353,16 +271,6 @@ __device__ __forceinline__ void dma_piece(uint8_t* lds_dst, const uint8_t* __res
         const uint8_t* src = gsrc + chunk * 1024 + lane * 16;
         RLT_DMA_ASM(dst, src);
     }
-}
-
-// branch-free form: the chunk index is clamped (a wavefront beyond the end re-copies the last chunk: the same bytes to the
-// same place), so that a tile body that issues pieces stays ONE basic block (sched_group_barrier patterns need that)
-template <int NBYTES>
-__device__ __forceinline__ void dma_piece_clamped(uint8_t* lds_dst, const uint8_t* __restrict__ gsrc, int wv, int lane, int c) {
-    const int chunk = min(wv + 8 * c, NBYTES / 1024 - 1);
-    const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)(lds_dst + chunk * 1024);
-    const uint8_t* src = gsrc + chunk * 1024 + lane * 16;
-    RLT_DMA_ASM(dst, src);
 }
 
 // Register fragments fetched from HBM before the tile loop must have ARRIVED before the loop: an empty asm statement
@@ -496,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
     constexpr int STAGE = Rec<HD>::RP + Rec<HD>::TP;                        // K rows pair | V transposed pair
     // TRV (head dim 64): P.V takes V^T by transposed reads from the V ROWS image, which is copied in place of the transposed
     // image (same size at head dim 64); the prepare pass then writes no transposed image of V either
-    constexpr bool TRV = RLT_FWD_TRV != 0 && HD == 64;
+    constexpr bool TRV = HD == 64;
     static_assert(!TRV || Rec<HD>::RP <= Rec<HD>::TP, "the V rows image must fit the stage slot of the transposed image");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint8_t* lds = reinterpret_cast<uint8_t*>(smem);
@@ -526,10 +434,8 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) c_m[r] = 0.f;
     // head dim 16: P.V on v_mfma_f32_16x16x32_bf16 (mma_T16), accumulators and normaliser per 16-query half
-    constexpr bool S16 = HD == 16 && RLT_HD16_SMALL_MFMA;
-    // padded 32x32x16 form at head dim 16 without dropout: the normaliser is row HD of O^T (T_rows above; with dropout
-    // P.V runs on the dropped P); 16x16x32 form without dropout: a ones-operand product sums P (LMFMA)
-    constexpr bool LROW = T_rows<HD>() > HD && !DROP && !S16;
+    constexpr bool S16 = HD == 16;
+    // without dropout a ones-operand product sums P (LMFMA); with dropout P.V runs on the dropped P
     constexpr bool LMFMA = S16 && !DROP;
     f32x4v o16[2], l16[2];
 #pragma unroll
@@ -552,22 +458,10 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
     dma_wait_barrier<asm_dma<HD>()>();
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
-        // head dim 64: the 4-5 LDS-DMA pieces of a wavefront are spread over the tile body instead of all 8 wavefronts
-        // issuing everything before their first MFMA (see the dK+dV kernel); a wavefront without queries issues at the top
-        constexpr bool SPREAD = RLT_FWD_SPREAD != 0 && HD == 64 && asm_dma<HD>() && !TRV;
-        const bool more = t + 1 < nt;
-        if (!SPREAD || !wave_live) { if (more) issue(t + 1, buf ^ 1); }
-        else if (DROP && more && tid < KT) htab[(buf ^ 1) * KT + tid] = rlt_col_hash(ps, (uint32_t)((t + 1) * KT + tid));
-        const uint8_t* nk = record<HD>(g.img, 1, npair, nt, pair, min(t + 1, nt - 1));
-        const uint8_t* nv = record<HD>(g.img, 2, npair, nt, pair, min(t + 1, nt - 1)) + Rec<HD>::RP;
-        uint8_t* nl = lds + (buf ^ 1) * STAGE;
-        auto piece = [&](int pc) {                    // 0..2: K rows image, 3..5: V transposed image
-            if (!SPREAD || !more) return;
-            if (pc < 3) dma_piece<Rec<HD>::RP>(nl, nk, wv, lane, pc);
-            else dma_piece<Rec<HD>::TP>(nl + Rec<HD>::RP, nv, wv, lane, pc - 3);
-        };
+        // all 8 wavefronts issue the whole copy of the next tile here (its pieces spread over the tile body, as in the dK+dV
+        // kernel, measured +2 %)
+        if (t + 1 < nt) issue(t + 1, buf ^ 1);
         if (wave_live) {
-            piece(0);
             const uint16_t* k_hi = reinterpret_cast<const uint16_t*>(lds + buf * STAGE);
             const uint16_t* k_lo = k_hi + rows_elems<HD>();
             const uint16_t* v_hi = reinterpret_cast<const uint16_t*>(lds + buf * STAGE + Rec<HD>::RP);
@@ -580,7 +474,6 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
             // reference, so the result is the same softmax.  Per tile this saves 32 subtractions and 16*DT multiplies.
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) sc[sub] = mma_rows<HD>(k_hi, k_lo, sub, l31, hh, qh, ql, c_m);   // S^T[key][q] - m_ref
-            piece(1);
             if (t == nt - 1) {            // only the last tile can hold keys beyond B
 #pragma unroll
                 for (int sub = 0; sub < 2; ++sub)
@@ -617,7 +510,6 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) sc[sub][r] -= shift;
             }
-            piece(2);
             // per 32-key sub-tile: exponentiate, (drop), feed P.V - the second sub-tile's VALU work is issued while
             // the first sub-tile's MFMAs execute
             float psum = 0.f;
@@ -627,7 +519,7 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
                 for (int r = 0; r < 16; ++r) {
                     const float p = rlt_exp2(sc[sub][r]);
                     sc[sub][r] = p;
-                    if (!LROW && !LMFMA) psum += p;
+                    if (!LMFMA) psum += p;
                 }
                 if (DROP) {
                     const uint4* hk4 = reinterpret_cast<const uint4*>(htab + buf * KT + sub * 32 + 4 * hh);
@@ -640,13 +532,11 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
                         sc[sub][4 * gq + 3] = rlt_keep_rc(hq, hk.w, a.drop_thr) ? sc[sub][4 * gq + 3] * inv_keep : 0.f;
                     }
                 }
-                piece(3 + 2 * sub);
                 if (S16) mma_T16(v_hi, v_lo, sub, lane, sc[sub], o16, LMFMA ? l16 : nullptr);   // O^T[d][q] (+ sum of P)
                 else if (TRV) mma_Ttr<HD>(v_hi, v_lo, sub, lane, sc[sub], oacc);                // O^T[d][q], V^T read transposed
                 else mma_T<HD>(v_hi, v_lo, sub, l31, hh, sc[sub], oacc);                        // O^T[d][q]
-                if (sub == 0) piece(4);
             }
-            if (!LROW && !LMFMA) l_run += psum;
+            if (!LMFMA) l_run += psum;
         }
         dma_wait_barrier<asm_dma<HD>()>();
     }
@@ -667,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void attn3_fwd_kernel(Attn3Args g) {
         if (q < B && hh == 0) a.lse_o[((size_t)s * H + h) * B + q] = (m_run + log2f(l_own)) * LN2;
         return;
     }
-    const float l_tot = LROW ? oacc[0][8] : l_run + __shfl_xor(l_run, 32, 64);   // register 8 = row 16 (20 for the upper lane half)
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (q < B) {
         store_acc_T<HD>(a.o + ((size_t)s * B + q) * E + h * HD, hh, oacc, 1.f / l_tot);
         if (hh == 0) a.lse_o[((size_t)s * H + h) * B + q] = (m_run + log2f(l_tot)) * LN2;
@@ -711,7 +601,7 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
-    constexpr bool S16 = HD == 16 && RLT_HD16_SMALL_MFMA;         // dQ^T on v_mfma_f32_16x16x32_bf16 (mma_T16)
+    constexpr bool S16 = HD == 16;                                // dQ^T on v_mfma_f32_16x16x32_bf16 (mma_T16)
     f32x4v dq16[2];
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf)
@@ -728,16 +618,17 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
     for (int r = 0; r < 16; ++r) { c_lse[r] = SEED ? -lse2 : 0.f; c_del[r] = DROP ? 0.f : -del; }
     uint32_t* htab = reinterpret_cast<uint32_t*>(lds + 2 * STAGE);          // dropout: per-key hashes of the tile
     const uint32_t hq = DROP ? rlt_row_hash(ps, (uint32_t)q) : 0u;
-    // head dim 64: the 7-8 LDS-DMA pieces of a wavefront spread over the tile body (see the dK+dV kernel)
-    constexpr bool SPREAD = RLT_DQ_SPREAD != 0 && spread_dma<HD>();
+    // head dim 64: the 7-8 LDS-DMA pieces of a wavefront spread over the tile body (see the dK+dV kernel; measured -2 %)
+    constexpr bool SPREAD = asm_dma<HD>();
     auto issue = [&](int t, int buf) {
         dma_copy<KREC, asm_dma<HD>()>(lds + buf * STAGE, record<HD>(g.img, 1, npair, nt, pair, t), wv, lane);
         dma_copy<Rec<HD>::RP, asm_dma<HD>()>(lds + buf * STAGE + KREC, record<HD>(g.img, 2, npair, nt, pair, t), wv, lane);
         if (DROP && tid < KT) htab[buf * KT + tid] = rlt_col_hash(ps, (uint32_t)(t * KT + tid));
     };
-    // stepped body with transposed reads (head dim 64, no dropout): only the K and V ROWS images are copied - 36 chunks dealt
-    // as one list to the 8 wavefronts, 5 slots each (4 re-copy the last chunk), branch-free (see the dK+dV kernel)
-    constexpr bool DEAL = RLT_DQ_STEPPED != 0 && RLT_DQ_TRREAD != 0 && HD == 64 && !DROP && SPREAD;
+    // stepped body (head dim 64, no dropout; see the dK+dV kernel), K^T by ds_read_b64_tr_b16 from the K rows image: only the
+    // K and V ROWS images are copied - 36 chunks dealt as one list to the 8 wavefronts, 5 slots each (4 re-copy the last
+    // chunk), branch-free
+    constexpr bool STEPPED = HD == 64 && !DROP;
     auto deal_piece = [&](const uint8_t* nk, const uint8_t* nv, uint8_t* nl, int pc) {
         constexpr int NR = Rec<HD>::RP / 1024;
         const int id = min(wv + 8 * pc, 2 * NR - 1);
@@ -751,7 +642,7 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
     dma_wait_barrier<asm_dma<HD>()>();
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
-        if (DEAL && !wave_live) {                   // a wavefront without queries: its 5 slots of the dealt list, all at once
+        if (STEPPED && !wave_live) {                // a wavefront without queries: its 5 slots of the dealt list, all at once
             if (t + 1 < nt) {
 #pragma unroll
                 for (int pc = 0; pc < 5; ++pc)
@@ -770,14 +661,11 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
             const uint8_t* nk = record<HD>(g.img, 1, npair, nt, pair, min(t + 1, nt - 1));
             const uint8_t* nv = record<HD>(g.img, 2, npair, nt, pair, min(t + 1, nt - 1));
             uint8_t* nl = lds + ((t & 1) ^ 1) * STAGE;
-            // stepped body (head dim 64, no dropout; see the dK+dV kernel): K^T by ds_read_b64_tr_b16 from the K rows image
-            constexpr bool STEPPED = RLT_DQ_STEPPED != 0 && HD == 64 && !DROP && SPREAD;
-            constexpr bool TRREAD = STEPPED && RLT_DQ_TRREAD != 0;
             auto piece = [&](int pc) {                // 0..4: K record (rows + transposed), 5..7: V rows image
-                if (!SPREAD || (!more && !TRREAD)) return;      // (with TRREAD the last tile re-copies itself into the idle stage)
-                if (TRREAD) {
+                if (STEPPED) {                        // its 5 dealt slots (the last tile re-copies itself into the idle stage)
                     if (pc < 5) deal_piece(nk, nv, nl, pc);
-                } else if (pc < 5) dma_piece<KREC>(nl, nk, wv, lane, pc);
+                } else if (!SPREAD || !more) return;
+                else if (pc < 5) dma_piece<KREC>(nl, nk, wv, lane, pc);
                 else dma_piece<Rec<HD>::RP>(nl + KREC, nv, wv, lane, pc - 5);
             };
             if constexpr (STEPPED) {
@@ -794,7 +682,7 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
                         const int off = (sub * 32 + l31) * (HD + 8) + 8 * hh + 16 * k;
                         fh[st] = *reinterpret_cast<const bf16x8*>(hi + off);
                         fl[st] = *reinterpret_cast<const bf16x8*>(lo + off);
-                    } else if (TRREAD) {              // A[d][k slot] = K[key][d], k = 2 s + dt (mapping as in the dK+dV kernel)
+                    } else {                          // A[d][k slot] = K[key][d], k = 2 s + dt (mapping as in the dK+dV kernel)
                         const int sub = (st - 16) >> 2;
                         const int krow = sub * 32 + 16 * (k >> 1) + 4 * hh + ((lane & 15) >> 2);
                         const int off = krow * (HD + 8) + 32 * (k & 1) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
@@ -802,16 +690,11 @@ __global__ __launch_bounds__(512, 2) void attn3_bwd_dq_kernel(Attn3Args g) {
                         const v4s l0 = tr_read(kr_lo + off), l1 = tr_read(kr_lo + off + 8 * (HD + 8));
                         fh[st] = cat_frag(h0, h1);
                         fl[st] = cat_frag(l0, l1);
-                    } else {
-                        const int sub = (st - 16) >> 2;
-                        const int off = ((k & 1) * 32 + l31) * LDT3 + sub * 32 + 16 * (k >> 1) + 8 * hh;
-                        fh[st] = as_frag(*reinterpret_cast<const uint4*>(kt_hi + off));
-                        fl[st] = as_frag(*reinterpret_cast<const uint4*>(kt_lo + off));
                     }
                 };
                 auto mm = [&](int st) {
                     const int k = st & 3;
-                    if (st % RLT_DQ_SPREAD_EVERY == 0) piece(st / RLT_DQ_SPREAD_EVERY);
+                    if (st % DQ_SPREAD_EVERY == 0) piece(st / DQ_SPREAD_EVERY);
                     if (st + 2 < 24) frag(st + 2);
                     if (st < 16) {
                         const int sub = st >> 3;
@@ -976,11 +859,12 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
         dma_copy<STAGE - QREC, asm_dma<HD>()>(lds + buf * STAGE + QREC, record<HD>(g.dimg, 0, npair, nt, pair, t), wv, lane);   // whole dO record
         if (DROP && tid < KT) htab[buf * KT + tid] = rlt_row_hash(ps, (uint32_t)(t * KT + tid));
     };
-    // TRREAD (stepped head-dim-64 body): the dV / dK products take their A operands from the ROWS images with
+    // STEPPED (head dim 64, no dropout; with dropout the stepped body is 18 % slower than the compiler-scheduled one: 6.55 vs
+    // 5.57 ms): the dV / dK products take their A operands from the ROWS images with
     // ds_read_b64_tr_b16, so the transposed images are not copied at all.  The 37 chunks of a tile - Q rows image 18, dO rows
     // image 18, aux block 1 - are ONE list dealt to the 8 wavefronts, 5 slots each (3 of the 40 re-copy the aux chunk);
     // source and destination follow from the chunk id by selects: branch-free, so that the tile body stays one basic block.
-    constexpr bool TRREAD = RLT_DKV_TRREAD != 0 && RLT_STEPPED != 0 && HD == 64 && !DROP;
+    constexpr bool STEPPED = HD == 64 && !DROP;
     auto deal_piece = [&](const uint8_t* nq, const uint8_t* nd, uint8_t* nl, int pc) {
         constexpr int NR = Rec<HD>::RP / 1024;
         const int id = min(wv + 8 * pc, 2 * NR);
@@ -997,17 +881,15 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
         RLT_STAMP(0);
         // The copy of tile t+1 is spread over the tile body (below): all 8 wavefronts issuing their ~10 pieces at the top of the
         // tile cost every one of them ~1,500 cycles before the first MFMA (timeline stamps).  A wavefront without keys runs no
-        // matrix steps and issues its pieces here.
-        constexpr bool SPREAD = RLT_STEPPED_SPREAD != 0 && spread_dma<HD>() && (HD != 64 || (RLT_STEPPED != 0 && !DROP));
-        if (SPREAD && TRREAD && !wave_live) {        // its 5 slots of the dealt list, all at once
+        // matrix steps and issues its pieces here.  The other bodies issue the whole copy here.
+        if (STEPPED && !wave_live) {                 // its 5 slots of the dealt list, all at once
             if (t + 1 < nt) {
                 const uint8_t* nq1 = record<HD>(g.img, 0, npair, nt, pair, t + 1);
                 const uint8_t* nd1 = record<HD>(g.dimg, 0, npair, nt, pair, t + 1);
 #pragma unroll
                 for (int pc = 0; pc < 5; ++pc) deal_piece(nq1, nd1, lds + (buf ^ 1) * STAGE, pc);
             }
-        } else if (!SPREAD || !wave_live) { if (t + 1 < nt) issue(t + 1, buf ^ 1); }
-        else if (DROP && t + 1 < nt && tid < KT) htab[(buf ^ 1) * KT + tid] = rlt_row_hash(ps, (uint32_t)((t + 1) * KT + tid));
+        } else if (!STEPPED) { if (t + 1 < nt) issue(t + 1, buf ^ 1); }
         if (wave_live) {
             const uint16_t* qr_hi = reinterpret_cast<const uint16_t*>(lds + buf * STAGE);
             const uint16_t* qr_lo = qr_hi + rows_elems<HD>();
@@ -1019,27 +901,19 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
             const uint16_t* dt_lo = dt_hi + T_elems<HD>();
             const float* Ls = reinterpret_cast<const float*>(lds + buf * STAGE + 2 * QREC);
             const float* Es = Ls + KT;
-            const bool more = SPREAD && t + 1 < nt;
-            // piece pc (0..9) of this wavefront's share of the copy of tile t+1: 5 pieces of the Q record, 5 of the dO
-            // record; the record addresses are computed once per tile (address arithmetic inside the bursts cost 15 %)
-            const uint8_t* nq = record<HD>(g.img, 0, npair, nt, pair, min(t + 1, nt - 1));
-            const uint8_t* nd = record<HD>(g.dimg, 0, npair, nt, pair, min(t + 1, nt - 1));
-            uint8_t* nl = lds + (buf ^ 1) * STAGE;
-            auto next_piece = [&](int pc) {
-                if (!more && !TRREAD) return;
-                if (TRREAD) {                     // (the last tile re-copies itself into the idle stage)
-                    if (pc < 5) deal_piece(nq, nd, nl, pc);
-                } else if (pc < 5) dma_piece<QREC>(nl, nq, wv, lane, pc);
-                else dma_piece<STAGE - QREC>(nl + QREC, nd, wv, lane, pc - 5);
-            };
-#if RLT_STEPPED
-            if constexpr (HD == 64 && !DROP) {     // (with dropout the stepped body is 18 % slower than the compiler-scheduled one: 6.55 vs 5.57 ms)
+            if constexpr (STEPPED) {
+                // this wavefront's 5 dealt slots of the copy of tile t+1 go out between the matrix steps (the last tile re-copies
+                // itself into the idle stage); the record addresses are computed once per tile (address arithmetic inside the
+                // bursts cost 15 %)
+                const uint8_t* nq = record<HD>(g.img, 0, npair, nt, pair, min(t + 1, nt - 1));
+                const uint8_t* nd = record<HD>(g.dimg, 0, npair, nt, pair, min(t + 1, nt - 1));
+                uint8_t* nl = lds + (buf ^ 1) * STAGE;
                 // The 32 matrix steps of a tile (3 MFMAs each) as an explicit software pipeline over the two 32-query
                 // sub-tiles a, b:   [S_a dP_a] [S_b dP_b | E_a] [dV_a dK_a | E_b] [dV_b dK_b]
                 // E_x = exp, dS and the bf16 splits of sub-tile x, cut into per-step chunks of a few vector instructions that
                 // sit in the MFMA gaps of the OTHER sub-tile's products (left to itself hipcc keeps program order: the
                 // element-wise block runs between the products it separates and the matrix pipe idles meanwhile - measured
-                // tile time = MFMA cycles + vector issue cycles).  The LDS fragments of step i + RLT_STEPPED are read while
+                // tile time = MFMA cycles + vector issue cycles).  The LDS fragments of step i + PREFETCH are read while
                 // step i multiplies; a full scheduling fence after every step pins all of it.
                 bf16x8 fh[32], fl[32];
                 f32x16 sc2[2], dp2[2];
@@ -1052,7 +926,7 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
                         const int off = (sub * 32 + l31) * (HD + 8) + 8 * hh + 16 * k;
                         fh[st] = *reinterpret_cast<const bf16x8*>(hi + off);
                         fl[st] = *reinterpret_cast<const bf16x8*>(lo + off);
-                    } else if (TRREAD) {
+                    } else {
                         // A[d][k-slot j] = X[query][d] read transposed from the rows image: k = 2 s + dt; the 16-lane group
                         // (lane >> 4) covers d = 32 dt + 16 (group & 1) + (lane & 15); its lane 4q + p supplies the address of
                         // row q, columns 4p..4p+3 of the 4 x 16 block and receives column (lane & 15).  The k slots of lane half
@@ -1066,12 +940,6 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
                         const v4s l0 = tr_read(lo + off), l1 = tr_read(lo + off + 8 * (HD + 8));
                         fh[st] = cat_frag(h0, h1);
                         fl[st] = cat_frag(l0, l1);
-                    } else {
-                        const uint16_t* hi = prod == 2 ? dt_hi : qt_hi;
-                        const uint16_t* lo = prod == 2 ? dt_lo : qt_lo;
-                        const int off = ((k & 1) * 32 + l31) * LDT3 + sub * 32 + 16 * (k >> 1) + 8 * hh;   // k = 2 s + dt
-                        fh[st] = as_frag(*reinterpret_cast<const uint4*>(hi + off));
-                        fl[st] = as_frag(*reinterpret_cast<const uint4*>(lo + off));
                     }
                 };
                 auto seed = [&](int sub) {                   // accumulators start at -lse[q] and -delta[q]
@@ -1083,13 +951,12 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
                     }
                 };
 #pragma unroll
-                for (int i = 0; i < RLT_STEPPED; ++i) frag(i);
+                for (int i = 0; i < PREFETCH; ++i) frag(i);
                 seed(0);
-                auto mm = [&](int st) {                      // the fragment reads of step st + RLT_STEPPED and the 3 MFMAs of step st
+                auto mm = [&](int st) {                      // the fragment reads of step st + PREFETCH and the 3 MFMAs of step st
                     const int sub = (st >> 3) & 1, prod = (st >> 4) * 2 + ((st >> 2) & 1), k = st & 3;
-                    if (RLT_SPREAD_EVERY > 0 && st % (RLT_SPREAD_EVERY > 0 ? RLT_SPREAD_EVERY : 1) == 0 && st / (RLT_SPREAD_EVERY > 0 ? RLT_SPREAD_EVERY : 1) < 10)
-                        next_piece(st / (RLT_SPREAD_EVERY > 0 ? RLT_SPREAD_EVERY : 1));
-                    if (st + RLT_STEPPED < 32) frag(st + RLT_STEPPED);
+                    if (st % SPREAD_EVERY == 0 && st / SPREAD_EVERY < 5) deal_piece(nq, nd, nl, st / SPREAD_EVERY);
+                    if (st + PREFETCH < 32) frag(st + PREFETCH);
                     if (prod == 0) sc2[sub] = mfma3(fh[st], fl[st], kh[k], kl[k], sc2[sub]);           // S[q][key] - lse
                     else if (prod == 1) dp2[sub] = mfma3(fh[st], fl[st], vh[k], vl[k], dp2[sub]);      // dP[q][key] (- delta)
                     else if (prod == 2) dv[k & 1] = mfma3(fh[st], fl[st], ph[sub][k >> 1], pl[sub][k >> 1], dv[k & 1]);   // dV^T += dO^T P
@@ -1162,7 +1029,6 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
 #pragma unroll
                 for (int st = 28; st < 32; ++st) { mm(st); pattern(); }                                               // dK_b
             } else {
-#endif
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 // the accumulators start at -lse[q] and -delta[q] (the aux block of the dO record holds them negated),
@@ -1175,11 +1041,8 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
                     sc[r] = Ls[ql];
                     dp[r] = DROP ? 0.f : Es[ql];
                 }
-                next_piece(5 * sub);
                 sc = mma_rows<HD>(qr_hi, qr_lo, sub, l31, hh, kh, kl, sc);       // S[q][key] - lse (Q carries scale*log2e)
-                next_piece(5 * sub + 1);
                 dp = mma_rows<HD>(dr_hi, dr_lo, sub, l31, hh, vh, vl, dp);       // dP[q][key] (- delta)
-                next_piece(5 * sub + 2);
                 // queries beyond B need no mask: their columns of the transposed Q / dO images are zero, p is finite
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -1196,26 +1059,21 @@ __global__ __launch_bounds__(512) void attn3_bwd_dkv_kernel(Attn3Args g) {
                     }
                     sc[r] = p;
                 }
-                next_piece(5 * sub + 3);
-                if (HD == 16 && RLT_HD16_SMALL_MFMA) {
+                if (HD == 16) {
                     mma_T16(dt_hi, dt_lo, sub, lane, sc, dv16);                    // dV^T[d][key] += dO^T P
-                    next_piece(5 * sub + 4);
                     mma_T16(qt_hi, qt_lo, sub, lane, dp, dk16);                    // dK^T[d][key] += (c Q)^T dS
                 } else {
                     mma_T<HD>(dt_hi, dt_lo, sub, l31, hh, sc, dv);                 // dV^T[d][key] += dO^T P
-                    next_piece(5 * sub + 4);
                     mma_T<HD>(qt_hi, qt_lo, sub, l31, hh, dp, dk);                 // dK^T[d][key] += (c Q)^T dS
                 }
             }
-#if RLT_STEPPED
             }
-#endif
         }
         RLT_STAMP(1);
         dma_wait_barrier<asm_dma<HD>()>();
     }
     if (!wave_live) return;
-    if (HD == 16 && RLT_HD16_SMALL_MFMA) {          // D[row = d = 4 (lane >> 4) + r][col = lane & 15]: one float4 per lane and 16-key half
+    if (HD == 16) {                                 // D[row = d = 4 (lane >> 4) + r][col = lane & 15]: one float4 per lane and 16-key half
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
             const int kk = ktile * QT3 + wv * 32 + 16 * hf + (lane & 15);
@@ -1276,13 +1134,11 @@ int run3(int which, const AttnArgs& a, void* images, void* dimages, hipStream_t 
         p.src[0] = a.qkv; p.src[1] = a.qkv + E; p.src[2] = a.qkv + 2 * E;
         p.mul[0] = a.scale * LOG2E; p.mul[1] = 1.f; p.mul[2] = 1.f;
         p.ld = (size_t)3 * E; p.out = (uint8_t*)images; p.S = a.S; p.B = a.B; p.H = a.H; p.nmat = 3;
-        p.perm16[0] = p.perm16[1] = p.perm16[2] = HD == 16 && RLT_HD16_SMALL_MFMA;   // head dim 16: every transposed image feeds mma_T16
+        p.perm16[0] = p.perm16[1] = p.perm16[2] = HD == 16;   // head dim 16: every transposed image feeds mma_T16
         // head dim 64 without dropout: the stepped dK+dV and dQ bodies read Q^T and K^T transposed from the rows images
         // (ds_read_b64_tr_b16), so those two images are not written (V^T is: the forward kernel's P.V operand)
-        constexpr bool TR_ALL = HD == 64 && RLT_STEPPED != 0 && RLT_DKV_TRREAD != 0 && RLT_STEPPED_SPREAD != 0 &&
-                                RLT_DQ_STEPPED != 0 && RLT_DQ_TRREAD != 0 && RLT_DQ_SPREAD != 0 && spread_dma<HD>();
-        p.skip_t[0] = p.skip_t[1] = TR_ALL && a.drop_p == 0.f;
-        p.skip_t[2] = HD == 64 && RLT_FWD_TRV != 0;          // V^T: only the forward kernel's P.V used it
+        p.skip_t[0] = p.skip_t[1] = HD == 64 && a.drop_p == 0.f;
+        p.skip_t[2] = HD == 64;                              // V^T: only the forward kernel's P.V used it
         int rc = prepare3<HD>(p, st);
         if (rc) return rc;
     } else if (which == 3) {     // backward prepare: split dO (+ lse, delta)
@@ -1291,11 +1147,10 @@ int run3(int which, const AttnArgs& a, void* images, void* dimages, hipStream_t 
         p.lse = a.lse; p.delta = a.delta;
         p.o = a.o; p.delta_out = const_cast<float*>(a.delta);     // with a.o set: delta is computed by the prepare pass
         p.out = (uint8_t*)dimages; p.S = a.S; p.B = a.B; p.H = a.H; p.nmat = 1;
-        p.perm16[0] = HD == 16 && RLT_HD16_SMALL_MFMA;       // dO^T likewise
+        p.perm16[0] = HD == 16;                              // dO^T likewise
         // dO^T is read transposed from the rows image by the stepped dK+dV body; the caller says so with drop_p == 0
         // (rlt_list_attention_bwd and, since ABI 5, the stand-alone prepare entry point: both are given the forward call's drop_p)
-        constexpr bool TR_DKV = HD == 64 && RLT_STEPPED != 0 && RLT_DKV_TRREAD != 0 && RLT_STEPPED_SPREAD != 0 && spread_dma<HD>();
-        p.skip_t[0] = TR_DKV && a.drop_p == 0.f;
+        p.skip_t[0] = HD == 64 && a.drop_p == 0.f;
         return prepare3<HD>(p, st);
     }
     return a.drop_p > 0.f ? launch3<HD, true>(which, g, st) : launch3<HD, false>(which, g, st);

@@ -26,53 +26,11 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-
 // per head dim: bf16 elements per image row (HD + 8: 16-byte aligned fragments, rows 16 bytes apart in the banks), per plane,
 // per tile image [h | m | l]
 template <int HD> constexpr int ldr6() { return HD + 8; }
 template <int HD> constexpr int plane6() { return KT * (HD + 8); }
 template <int HD> constexpr int img6() { return 3 * KT * (HD + 8); }
-
-__device__ __forceinline__ uint32_t pk2_6(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-// exact three-way split of four values (see gemm.hip split4x3)
-__device__ __forceinline__ void split4x3_6(float a, float b, float c, float d, uint2& hi, uint2& mid, uint2& lo) {
-    hi.x = pk2_6(a, b);
-    hi.y = pk2_6(c, d);
-    asm("" : "+v"(hi.x), "+v"(hi.y));
-    const float ra = a - __builtin_bit_cast(float, hi.x << 16), rb = b - __builtin_bit_cast(float, hi.x & 0xffff0000u);
-    const float rc = c - __builtin_bit_cast(float, hi.y << 16), rd = d - __builtin_bit_cast(float, hi.y & 0xffff0000u);
-    mid.x = pk2_6(ra, rb);
-    mid.y = pk2_6(rc, rd);
-    asm("" : "+v"(mid.x), "+v"(mid.y));
-    lo.x = pk2_6(ra - __builtin_bit_cast(float, mid.x << 16), rb - __builtin_bit_cast(float, mid.x & 0xffff0000u));
-    lo.y = pk2_6(rc - __builtin_bit_cast(float, mid.y << 16), rd - __builtin_bit_cast(float, mid.y & 0xffff0000u));
-}
-struct Frag3 { bf16x8 h, m, l; };
-__device__ __forceinline__ Frag3 split8x3(const float (&x)[8]) {
-    uint2 h0, m0, l0, h1, m1, l1;
-    split4x3_6(x[0], x[1], x[2], x[3], h0, m0, l0);
-    split4x3_6(x[4], x[5], x[6], x[7], h1, m1, l1);
-    Frag3 f;
-    f.h = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-    f.m = __builtin_bit_cast(bf16x8, make_uint4(m0.x, m0.y, m1.x, m1.y));
-    f.l = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-    return f;
-}
-__device__ __forceinline__ f32x16 mfma6(const Frag3& a, const Frag3& b, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, c, 0, 0, 0);
-    return c;
-}
 
 // ---- staging: a [64 rows][HD] fp32 tile -> registers (HD / 16 float4 per thread) -> three-plane image
 template <int HD> struct Stage6 { float4 v[HD / 16]; };
@@ -93,7 +51,7 @@ __device__ __forceinline__ void stage6_store(uint16_t* __restrict__ img, int tid
     for (int i = 0; i < HD / 16; ++i) {
         const int idx = tid + 256 * i;
         uint2 h, m, l;
-        split4x3_6(st.v[i].x * mul, st.v[i].y * mul, st.v[i].z * mul, st.v[i].w * mul, h, m, l);
+        split4x3<true>(st.v[i].x * mul, st.v[i].y * mul, st.v[i].z * mul, st.v[i].w * mul, h, m, l);
         const int off = (idx / (HD / 4)) * ldr6<HD>() + 4 * (idx % (HD / 4));
         *reinterpret_cast<uint2*>(img + off) = h;
         *reinterpret_cast<uint2*>(img + plane6<HD>() + off) = m;
@@ -147,7 +105,7 @@ __global__ __launch_bounds__(256) void attn6_prepare_kernel(const float* __restr
     for (int i = 0; i < HD / 16; ++i) {
         const int idx = tid + 256 * i;
         uint2 hh_, mm_, ll_;
-        split4x3_6(st.v[i].x, st.v[i].y, st.v[i].z, st.v[i].w, hh_, mm_, ll_);
+        split4x3<true>(st.v[i].x, st.v[i].y, st.v[i].z, st.v[i].w, hh_, mm_, ll_);
         const int off = (idx / (HD / 4)) * ldr6<HD>() + 4 * (idx % (HD / 4));
         *reinterpret_cast<uint2*>(rec + off) = hh_;
         *reinterpret_cast<uint2*>(rec + plane6<HD>() + off) = mm_;
@@ -163,7 +121,7 @@ __device__ __forceinline__ void row_frags6(const float* __restrict__ rowp, int h
         const float4 v0 = *reinterpret_cast<const float4*>(rowp + 16 * ks + 8 * hh);
         const float4 v1 = *reinterpret_cast<const float4*>(rowp + 16 * ks + 8 * hh + 4);
         const float x[8] = {v0.x * mul, v0.y * mul, v0.z * mul, v0.w * mul, v1.x * mul, v1.y * mul, v1.z * mul, v1.w * mul};
-        f[ks] = split8x3(x);
+        f[ks] = split8x3<true>(x);
     }
 }
 
@@ -183,14 +141,6 @@ __device__ __forceinline__ f32x16 mma_rows6(const uint16_t* __restrict__ img, in
     return acc;
 }
 
-__device__ __forceinline__ v4s tr_read6(const uint16_t* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(p));
-}
-__device__ __forceinline__ bf16x8 cat_frag6(v4s a, v4s b) {
-    typedef short v8s __attribute__((ext_vector_type(8)));
-    const v8s v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
 // acc[dt] (D[row = d][col = lane]) += sum over the 32 rows of sub-tile `sub` of  image[row][d] * w[row][lane]:
 // A operand = the image read TRANSPOSED (ds_read_b64_tr_b16: the 16-lane group (lane >> 4) covers d = 32 dt + 16 (group & 1) +
 // (lane & 15); the k slots of lane half hh are rows 16 s + 4 hh + {0..3} and + 8 - the rows registers 8s..8s+7 of w hold),
@@ -205,15 +155,15 @@ __device__ __forceinline__ void mma_cols6(const uint16_t* __restrict__ img, int 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const float x[8] = {w[8 * s + 0], w[8 * s + 1], w[8 * s + 2], w[8 * s + 3], w[8 * s + 4], w[8 * s + 5], w[8 * s + 6], w[8 * s + 7]};
-        const Frag3 b = split8x3(x);
+        const Frag3 b = split8x3<true>(x);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
             const int row = sub * 32 + 16 * s + 4 * hh + ((lane & 15) >> 2);
             const int off = row * LDR + 32 * dt + (HD >= 32 ? 16 * ((lane >> 4) & 1) : 0) + 4 * (lane & 3);
             Frag3 a;
-            a.h = cat_frag6(tr_read6(img + off), tr_read6(img + off + 8 * LDR));
-            a.m = cat_frag6(tr_read6(img + PL + off), tr_read6(img + PL + off + 8 * LDR));
-            a.l = cat_frag6(tr_read6(img + 2 * PL + off), tr_read6(img + 2 * PL + off + 8 * LDR));
+            a.h = cat_frag(tr_read(img + off), tr_read(img + off + 8 * LDR));
+            a.m = cat_frag(tr_read(img + PL + off), tr_read(img + PL + off + 8 * LDR));
+            a.l = cat_frag(tr_read(img + 2 * PL + off), tr_read(img + 2 * PL + off + 8 * LDR));
             acc[dt] = mfma6(a, b, acc[dt]);
         }
     }
@@ -363,18 +313,13 @@ __global__ __launch_bounds__(256, 2) void attn6_fwd_kernel(AttnArgs a) {
 //   slot:   4t     4t+1   4t+2   4t+3   4t+4
 //   A:      X(t)   Y(t)   Z(t)   W(t)   X(t+1)       (A stages K, into the other image buffer)
 //   B:      W(t-1) X(t)   Y(t)   Z(t)   W(t)         (B stages V)
-// so every slot pairs a matrix segment with a vector segment on each SIMD; `s_nop` behind every MFMA of X and Z (RLT_A6_PP_PAD).
+// so every slot pairs a matrix segment with a vector segment on each SIMD; `s_nop 1` behind every MFMA of X and Z (pp_pad).
 // Measured (4096 x 60 positions, s_memtime stamps of a -DRLT_PP_STAMPS build, tools/pp_stamps.py): the four slots of a tile take
 // ~1830 / 2110 / 1950-2200 / 2100-2500 cycles + 200-600 at each barrier, 9,700 per tile against 2 x 5,550 for two tiles of the
 // two-workgroup form: 5.55 -> 5.25 ms.  The slots are now as long as their VECTOR segments: the ~610 vector instructions per
 // wavefront and tile (softmax 130, split of P 176, exponentials 32, staging split + addresses 150, ...) do not fit the ~5 issue
 // slots that each of the partner's 96 MFMAs leaves - the kernel is vector-issue-bound, which is what is left to shorten.
-#ifndef RLT_A6_PP_PAD
-#define RLT_A6_PP_PAD 1
-#endif
-__device__ __forceinline__ void pp_pad(f32x16& c) {
-    if (RLT_A6_PP_PAD >= 0) asm volatile("s_nop %1" : "+v"(c) : "n"(RLT_A6_PP_PAD >= 0 ? RLT_A6_PP_PAD : 0));
-}
+__device__ __forceinline__ void pp_pad(f32x16& c) { asm volatile("s_nop 1" : "+v"(c)); }
 __device__ __forceinline__ f32x16 mfma6_pp(const Frag3& a, const Frag3& b, f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, c, 0, 0, 0); pp_pad(c);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, c, 0, 0, 0); pp_pad(c);
@@ -539,7 +484,7 @@ __global__ __launch_bounds__(512, 1) void attn6_fwd_pp_kernel(AttnArgs a) {
             for (int s2 = 0; s2 < 2; ++s2) {
                 const float x[8] = {sc[sub][8 * s2 + 0], sc[sub][8 * s2 + 1], sc[sub][8 * s2 + 2], sc[sub][8 * s2 + 3],
                                     sc[sub][8 * s2 + 4], sc[sub][8 * s2 + 5], sc[sub][8 * s2 + 6], sc[sub][8 * s2 + 7]};
-                pf[sub][s2] = split8x3(x);
+                pf[sub][s2] = split8x3<true>(x);
             }
     };
     auto seg_z = [&](int t) {
@@ -549,9 +494,9 @@ __global__ __launch_bounds__(512, 1) void attn6_fwd_pp_kernel(AttnArgs a) {
             const int row = sub * 32 + 16 * s2 + 4 * hh + ((lane & 15) >> 2);
             const int off = row * LDR + 32 * dt + (HD >= 32 ? 16 * ((lane >> 4) & 1) : 0) + 4 * (lane & 3);
             Frag3 f;
-            f.h = cat_frag6(tr_read6(img + off), tr_read6(img + off + 8 * LDR));
-            f.m = cat_frag6(tr_read6(img + PL + off), tr_read6(img + PL + off + 8 * LDR));
-            f.l = cat_frag6(tr_read6(img + 2 * PL + off), tr_read6(img + 2 * PL + off + 8 * LDR));
+            f.h = cat_frag(tr_read(img + off), tr_read(img + off + 8 * LDR));
+            f.m = cat_frag(tr_read(img + PL + off), tr_read(img + PL + off + 8 * LDR));
+            f.l = cat_frag(tr_read(img + 2 * PL + off), tr_read(img + 2 * PL + off + 8 * LDR));
             return f;
         };
         constexpr int NG = 4 * DT;
@@ -777,7 +722,7 @@ __device__ __forceinline__ void stage1_store(uint16_t* __restrict__ img, int tid
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         uint2 h, m, l;
-        split4x3_6(st.v[i].x, st.v[i].y, st.v[i].z, st.v[i].w, h, m, l);
+        split4x3<true>(st.v[i].x, st.v[i].y, st.v[i].z, st.v[i].w, h, m, l);
         store_unit1(img, tid, i, h, m, l);
     }
 }
@@ -827,15 +772,14 @@ __device__ __forceinline__ void read_y1(int k, int sub, int s, int dt, int lane,
     const int row = sub * 32 + 16 * s + 4 * hh + ((lane & 15) >> 2) + 8 * (k & 1);
     const int off = img1_off(row, 32 * dt + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
     const int pl = k < 2 ? 1 : k < 4 ? 2 : 0;
-    trv[pl][k & 1] = tr_read6(img + pl * PL1 + off);
+    trv[pl][k & 1] = tr_read(img + pl * PL1 + off);
 }
 // operands of product i of a Y step: the transposed fragment; the split units of the two halves of a k-step (BY VALUE: through
 // references hipcc promotes u0 to registers too late, a widened 16-byte load keeps it in scratch - 64 stores and 37 loads per tile body)
-__device__ __forceinline__ bf16x8 cat2_6(uint2 a, uint2 b) { return __builtin_bit_cast(bf16x8, make_uint4(a.x, a.y, b.x, b.y)); }
-__device__ __forceinline__ bf16x8 y_frag_a(const v4s (&trv)[3][2], int i) { return cat_frag6(trv[x6_plane_a(i)][0], trv[x6_plane_a(i)][1]); }
+__device__ __forceinline__ bf16x8 y_frag_a(const v4s (&trv)[3][2], int i) { return cat_frag(trv[x6_plane_a(i)][0], trv[x6_plane_a(i)][1]); }
 __device__ __forceinline__ bf16x8 y_frag_b(const Split6 u0, const Split6 u1, int i) {
     const int bp = x6_plane_b(i);
-    return bp == 0 ? cat2_6(u0.hi, u1.hi) : bp == 1 ? cat2_6(u0.mid, u1.mid) : cat2_6(u0.lo, u1.lo);
+    return bp == 0 ? cat2(u0.hi, u1.hi) : bp == 1 ? cat2(u0.mid, u1.mid) : cat2(u0.lo, u1.lo);
 }
 // The S / dP products as asm statements: accumulator in VGPRs (the element-wise chunks read it there - as a builtin hipcc puts it into
 // AGPRs and every element costs a v_accvgpr_read), stationary fragments in AGPRs where b_agpr (pin_agpr).  hipcc does not see an MFMA in

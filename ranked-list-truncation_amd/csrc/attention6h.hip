@@ -17,58 +17,20 @@
 // hardware's 16-lane groups mix rows {0-3, 12-15} at g with rows {4-11} at g ^ 1) and the transposed fragments
 // (ds_read_b64_tr_b16: 32 lanes read 8 consecutive rows x 2 adjacent units).
 #include "attention_common.h"
+#include "split6.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
 
 constexpr int KTH = 64;                      // rows per tile
 constexpr int PLH = KTH * 64;                // bf16 elements per plane of a tile image (8 KiB)
 constexpr int IMGH = 3 * PLH;                // ... per image (h | m | l): 24 KiB
 constexpr int RECH = IMGH * 2;               // bytes per image record: 24 LDS-DMA pieces of 1 KiB
 
-__device__ __forceinline__ uint32_t pk2h(float a, float b) {
-    // the cast form: hipcc emits v_cvt_pk_bf16_f32 and inserts the wait states an MFMA needs behind a vector write of its operand
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ float lo16h(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi16h(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-__device__ __forceinline__ bf16x8 frag4h(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return __builtin_bit_cast(bf16x8, make_uint4(a, b, c, d)); }
 __device__ __forceinline__ f32x4 mmh(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-// exact three-way split in vector code (prepare pass and the stationary fragments only): eight values -> three fragments
-__device__ __forceinline__ void split8h(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float a = x[2 * i], b = x[2 * i + 1];
-        hh[i] = pk2h(a, b);
-        const float ra = a - lo16h(hh[i]), rb = b - hi16h(hh[i]);
-        mm[i] = pk2h(ra, rb);
-        ll[i] = pk2h(ra - lo16h(mm[i]), rb - hi16h(mm[i]));
-    }
-    h = frag4h(hh[0], hh[1], hh[2], hh[3]);
-    m = frag4h(mm[0], mm[1], mm[2], mm[3]);
-    l = frag4h(ll[0], ll[1], ll[2], ll[3]);
-}
 
 // swizzle of the 16-byte unit index by the row
 __host__ __device__ inline int swz(int row) { return 2 * ((row >> 1) & 3); }
-
-// max / sum over the four lanes (l & 15) + 16 {0, 1, 2, 3} that share a column
-__device__ __forceinline__ float col_max4h(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float col_sum4h(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
 
 // ---- pre-split tile images -----------------------------------------------------------------------------------------------------
 // One workgroup per (matrix, pair, tile): 64 rows x 64 d of fp32 -> the three-plane image in exactly the LDS layout.  ntile + 1
@@ -91,7 +53,7 @@ __global__ __launch_bounds__(256) void attn6h_prepare_kernel(const float* __rest
         const float x[8] = {ok ? v0.x : 0.f, ok ? v0.y : 0.f, ok ? v0.z : 0.f, ok ? v0.w : 0.f,
                             ok ? v1.x : 0.f, ok ? v1.y : 0.f, ok ? v1.z : 0.f, ok ? v1.w : 0.f};
         bf16x8 hh_, mm_, ll_;
-        split8h(x, hh_, mm_, ll_);
+        split8x3_by_pair(x, hh_, mm_, ll_);
         uint16_t* im = rec + r * 64 + ((c0 + u) ^ swz(r)) * 8;
         *reinterpret_cast<bf16x8*>(im) = hh_;
         *reinterpret_cast<bf16x8*>(im + PLH) = mm_;
@@ -111,10 +73,6 @@ __device__ unsigned long long a6h_stamps[4 * 4 * 18];
 #else
 #define A6H_STAMP(k) do { } while (0)
 #endif
-
-// the six plane products, smallest first: plane (0 = h, 1 = m, 2 = l) of the A and of the B operand
-__device__ __forceinline__ constexpr int prod_a(int p) { return p == 0 ? 1 : p == 1 ? 2 : p == 2 ? 0 : p == 3 ? 1 : 0; }
-__device__ __forceinline__ constexpr int prod_b(int p) { return p == 0 ? 1 : p == 1 ? 0 : p == 2 ? 2 : p == 3 ? 0 : p == 4 ? 1 : 0; }
 
 // ------------------------------------------------------------------------------------------ forward: one wavefront per SIMD
 // One 256-thread workgroup per CU owns 256 queries (a wavefront 64 = four blocks of 16).  Slot s of the tile body issues
@@ -160,8 +118,8 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
     {
         uint32_t s0[2] = {0u, 0u};
         if ((l15 >> 2) == g) s0[(l15 & 3) >> 1] = (l15 & 1) ? 0xBF800000u : 0x0000BF80u;       // -1.0 at element l15 & 3
-        sel[0] = frag4h(s0[0], s0[1], 0u, 0u);
-        sel[1] = frag4h(0u, 0u, s0[0], s0[1]);
+        sel[0] = frag4(s0[0], s0[1], 0u, 0u);
+        sel[1] = frag4(0u, 0u, s0[0], s0[1]);
     }
 
     // the lane's queries (scaled, log2 domain), stationary B operands of the score products: [own block][plane][k-step]
@@ -181,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
         for (int ks = 0; ks < 2; ++ks) {
             const float4 v0 = *reinterpret_cast<const float4*>(qp + 32 * ks + 8 * g), v1 = *reinterpret_cast<const float4*>(qp + 32 * ks + 8 * g + 4);
             const float x[8] = {v0.x * qmul, v0.y * qmul, v0.z * qmul, v0.w * qmul, v1.x * qmul, v1.y * qmul, v1.z * qmul, v1.w * qmul};
-            split8h(x, qf[n][0][ks], qf[n][1][ks], qf[n][2][ks]);
+            split8x3_by_pair(x, qf[n][0][ks], qf[n][1][ks], qf[n][2][ks]);
         }
 #pragma unroll
         for (int db = 0; db < 4; ++db) { acc[n][db] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[n][db] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -221,10 +179,10 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
             for (int p = 0; p < 6; ++p)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
-                    t = mmh(*reinterpret_cast<const bf16x8*>(img0 + prod_a(p) * PLH + 16 * kb * 64 + offR[ks]), qf[n][prod_b(p)][ks], t);
+                    t = mmh(*reinterpret_cast<const bf16x8*>(img0 + x6_plane_a(p) * PLH + 16 * kb * 64 + offR[ks]), qf[n][x6_plane_b(p)][ks], t);
             tmax = fmaxf(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])), tmax);
         }
-        m_ref[n] = col_max4h(tmax);
+        m_ref[n] = col_max4(tmax);
         seed_s[n] = f32x4{-m_ref[n], -m_ref[n], -m_ref[n], -m_ref[n]};
     }
 
@@ -242,7 +200,7 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < 3 * 4 * 4; ++i) (&pln[0][0][0])[i] = 0u;
 #pragma unroll
-    for (int i = 0; i < 12; ++i) (&kf[0][0][0])[i] = frag4h(0u, 0u, 0u, 0u);
+    for (int i = 0; i < 12; ++i) (&kf[0][0][0])[i] = frag4(0u, 0u, 0u, 0u);
 #pragma unroll
     for (int i = 0; i < 24; ++i) (&vt[0][0][0])[i] = v4s{0, 0, 0, 0};
 
@@ -279,20 +237,19 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
         };
         auto m_s = [&](int it, int n, int k) __attribute__((always_inline)) {
             const int kb = k / 12, p = (k % 12) / 2, ks = k % 2;
-            if (k % 12 == 0) mma_va_c(sc[it][kb], kf[kb][prod_a(p)][ks], qf[n][prod_b(p)][ks], seed_s[n]);
-            else mma_va(sc[it][kb], kf[kb][prod_a(p)][ks], qf[n][prod_b(p)][ks]);
+            if (k % 12 == 0) mma_va_c(sc[it][kb], kf[kb][x6_plane_a(p)][ks], qf[n][x6_plane_b(p)][ks], seed_s[n]);
+            else mma_va(sc[it][kb], kf[kb][x6_plane_a(p)][ks], qf[n][x6_plane_b(p)][ks]);
         };
         auto plane = [&](int lvl, int it) __attribute__((always_inline)) {
-            return frag4h(pln[lvl][it][0], pln[lvl][it][1], pln[lvl][it][2], pln[lvl][it][3]);
+            return frag4(pln[lvl][it][0], pln[lvl][it][1], pln[lvl][it][2], pln[lvl][it][3]);
         };
         auto m_r = [&](int it, int which, int level, int kb) __attribute__((always_inline)) {
             mma_av(sc[it][kb], sel[kb], plane(level - 1, it));
         };
         auto m_o = [&](int it, int n, int which, int k) __attribute__((always_inline)) {
             const int p = k >> 2, db = k & 3;
-            const v4s x = vt[prod_a(p)][db][0], y = vt[prod_a(p)][db][1];
-            const v8s av = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-            mma_out(p < 5 ? acc2[n][db] : acc[n][db], __builtin_bit_cast(bf16x8, av), plane(prod_b(p), it));
+            const v4s x = vt[x6_plane_a(p)][db][0], y = vt[x6_plane_a(p)][db][1];
+            mma_out(p < 5 ? acc2[n][db] : acc[n][db], cat_frag(x, y), plane(x6_plane_b(p), it));
         };
         auto e_exp = [&](int it, int kb, int r) __attribute__((always_inline)) { sc[it][kb][r] = rlt_exp2(sc[it][kb][r]); };
         // (chunks of the previous tile's last items: in the first body there is no previous tile - the ring holds zeros - and the weight must be 0, not exp2(0))
@@ -301,14 +258,13 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
         auto e_sum_p = [&](int it, int n, int kb, int r) __attribute__((always_inline)) { l_run[n] += sc[it][kb][r]; };
         auto c_pk = [&](int it, int which, int lvl, int j) __attribute__((always_inline)) {
             const f32x4& tile = sc[it][j >> 1];
-            pln[lvl][it][j] = pk2h(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
+            pln[lvl][it][j] = pk2(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
         };
         auto rd_row = [&](int mat, int kb, int pl, int ks, int b32) __attribute__((always_inline)) {
             kf[kb][pl][ks] = *reinterpret_cast<const bf16x8*>(Ic + pl * PLH + (32 * b32 + 16 * kb) * 64 + offR[ks]);
         };
         auto rd_tr = [&](int mat, int pl, int db, int half, int b32) __attribute__((always_inline)) {
-            vt[pl][db][half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (v4s __attribute__((address_space(3)))*)(Ic + IMGH + pl * PLH + (32 * b32 + 16 * half) * 64 + offT[db]));
+            vt[pl][db][half] = tr_read(Ic + IMGH + pl * PLH + (32 * b32 + 16 * half) * 64 + offT[db]);
         };
         auto st_dma = [&](int j) __attribute__((always_inline)) { dma(j, t_next, In); };
         const uint32_t* Hc = htab + cur * KTH;
@@ -338,7 +294,7 @@ __global__ __launch_bounds__(256, 1) void attn6h_fwd1_kernel(AttnArgs a) {
     float inv[NB], lse[NB];
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
-        const float l_tot = col_sum4h(l_run[n]);
+        const float l_tot = col_sum4(l_run[n]);
         bad |= !(l_tot > 0.f && l_tot <= 1.2676506e30f);         // 2^100: non-finite, vanished or far out of range -> redo with the moving reference
         inv[n] = 1.f / l_tot;
         lse[n] = (m_ref[n] + log2f(l_tot)) * LN2;

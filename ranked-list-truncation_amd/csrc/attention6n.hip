@@ -28,86 +28,35 @@
 #include "split6.h"
 #include <stdlib.h>
 
-#ifndef RLT_A6N_NB
-#define RLT_A6N_NB 4        // 16-row blocks owned by a wavefront (forward / dQ)
-#endif
-#ifndef RLT_A6N_NBK
-#define RLT_A6N_NBK 2       // ... in dK+dV (twice the stationary state per block)
-#endif
-#ifndef RLT_A6N_OCC
-#define RLT_A6N_OCC 2       // wavefronts per SIMD the register budget is declared for
-#endif
+namespace {
+
+constexpr int A6N_NB = 4;         // 16-row blocks owned by a wavefront (forward / dQ)
+constexpr int A6N_NBK = 2;        // ... in dK+dV (twice the stationary state per block)
+constexpr int A6N_OCC = 2;        // wavefronts per SIMD the register budget is declared for
+constexpr int A6N_OCC1 = 1;       // one wavefront per SIMD, 512 registers (compiled with -mllvm -amdgpu-mfma-vgpr-form: rlt_hip/build.py)
 
 // SEED (template parameter of the two-wavefront kernels; the pipelined kernels always): the row / lane constants (-m_run, -lse,
 // -delta) as the INITIAL accumulators of the score / dP products (as attention16.hip) - no subtraction per score.  It rounds every
 // partial sum at the magnitude of the constant: invisible next to the accumulation error of thousands of lists, 2-3x the error
 // of the unseeded form on a few dozen lists (profiles/r05_notes.md) - so launches of fewer than 512 lists run unseeded.  The same
-// launches also keep ONE accumulator per output (RLT_A6N_2ACC below): with one or two key blocks the second accumulator only adds
-// a rounding at full magnitude (whole-model gradient error 3.5x at 16 lists), what it removes needs thousands of lists to build up.
-#ifndef RLT_A6N_2ACC
-#define RLT_A6N_2ACC 1      // 1: the five small plane products of the list-contracted outputs (O, dQ, dK, dV) accumulate in their OWN accumulator, added to the h h' accumulator once at the end
-#endif
-#ifndef RLT_A6N_ABL
-#define RLT_A6N_ABL 0       // timing-only ablations of the dQ kernel (wrong results): 1 no element-wise work, 2 no split MFMAs, 4 no score / dP products, 8 no dQ product
-#endif
-#ifndef RLT_A6N_SGB
-#define RLT_A6N_SGB 0       // 1: sched_group_barrier pattern (1 MFMA, 2 vector) over the block body of dQ / dK+dV
-#endif
-// interleave hint for the scheduling region that ends here: NM x (one MFMA, NV vector instructions)
-template <int NM, int NV>
-__device__ __forceinline__ void interleave_hint() {
-#if RLT_A6N_SGB
-#pragma unroll
-    for (int i = 0; i < NM; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
-    }
-#endif
-}
-
-namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short v4s __attribute__((ext_vector_type(4)));
+// launches also keep ONE accumulator per output: with one or two key blocks the second accumulator only adds a rounding at full
+// magnitude (whole-model gradient error 3.5x at 16 lists), what it removes needs thousands of lists to build up.  With SEED the
+// five small plane products of the list-contracted outputs (O, dQ, dK, dV) accumulate in their OWN accumulator, added to the h h'
+// accumulator once at the end.
 
 constexpr int PLN = KT * 16;          // bf16 elements per plane of a tile image
 constexpr int IMGN = 3 * PLN;         // ... per image (h | m | l): 6 KiB
 
-__device__ __forceinline__ uint32_t pk2n(float a, float b) {
-    // the cast form: hipcc emits v_cvt_pk_bf16_f32 and inserts the wait states an MFMA needs behind a vector write of its operand
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ float lo16(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi16(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-#ifndef RLT_A6N_PAD
-#define RLT_A6N_PAD -1      // >= 0: `s_nop PAD` behind every MFMA (the issuing wavefront steps back from the SIMD's issue port: attention6.hip, RLT_A6_PP_PAD)
-#endif
-__device__ __forceinline__ f32x4 mm(bf16x8 a, bf16x8 b, f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    if (RLT_A6N_PAD >= 0) asm volatile("s_nop %1" : "+v"(c) : "n"(RLT_A6N_PAD >= 0 ? RLT_A6N_PAD : 0));
-    return c;
-}
-__device__ __forceinline__ bf16x8 frag4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return __builtin_bit_cast(bf16x8, make_uint4(a, b, c, d)); }
-
-// exact three-way split in vector code (staging and the stationary fragments only): four values -> three packed pairs
-__device__ __forceinline__ void split4v(float a, float b, float c, float d, uint2& h, uint2& m, uint2& l) {
-    h.x = pk2n(a, b); h.y = pk2n(c, d);
-    const float ra = a - lo16(h.x), rb = b - hi16(h.x), rc = c - lo16(h.y), rd = d - hi16(h.y);
-    m.x = pk2n(ra, rb); m.y = pk2n(rc, rd);
-    l.x = pk2n(ra - lo16(m.x), rb - hi16(m.x)); l.y = pk2n(rc - lo16(m.y), rd - hi16(m.y));
-}
+__device__ __forceinline__ f32x4 mm(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 struct Planes { bf16x8 h, m, l; };
 // ... of two 16 x 16 accumulator tiles on the matrix pipe (see the header): sel0 / sel1 select the tile
 __device__ __forceinline__ bf16x8 pack8(const f32x4& t0, const f32x4& t1) {
-    return frag4(pk2n(t0[0], t0[1]), pk2n(t0[2], t0[3]), pk2n(t1[0], t1[1]), pk2n(t1[2], t1[3]));
+    return frag4(pk2(t0[0], t0[1]), pk2(t0[2], t0[3]), pk2(t1[0], t1[1]), pk2(t1[2], t1[3]));
 }
 __device__ __forceinline__ Planes split_mx(f32x4 t0, f32x4 t1, bf16x8 sel0, bf16x8 sel1) {
     Planes p;
     p.h = pack8(t0, t1);
-    if (RLT_A6N_ABL & 2) { p.m = pack8(t1, t0); p.l = pack8(t0, t0); return p; }
     t0 = mm(sel0, p.h, t0); t1 = mm(sel1, p.h, t1);
     p.m = pack8(t0, t1);
     t0 = mm(sel0, p.m, t0); t1 = mm(sel1, p.m, t1);
@@ -115,7 +64,7 @@ __device__ __forceinline__ Planes split_mx(f32x4 t0, f32x4 t1, bf16x8 sel0, bf16
     return p;
 }
 // acc += A^T-image planes x fresh planes: the six products, smallest first
-// ... with the small products in their own accumulator (RLT_A6N_2ACC)
+// ... with the small products in their own accumulator (SEED)
 __device__ __forceinline__ void mm6_2(const Planes& a, const Planes& b, f32x4& big, f32x4& small) {
     small = mm(a.m, b.m, small);
     small = mm(a.l, b.h, small);
@@ -160,8 +109,8 @@ __device__ __forceinline__ void own_frags(const float* __restrict__ rowp, const 
     const float4 v0 = *reinterpret_cast<const float4*>(rowp + 8 * (c.g & 1));
     const float4 v1 = *reinterpret_cast<const float4*>(rowp + 8 * (c.g & 1) + 4);
     uint2 h0, m0, l0, h1, m1, l1;
-    split4v(v0.x * mul, v0.y * mul, v0.z * mul, v0.w * mul, h0, m0, l0);
-    split4v(v1.x * mul, v1.y * mul, v1.z * mul, v1.w * mul, h1, m1, l1);
+    split4x3<false>(v0.x * mul, v0.y * mul, v0.z * mul, v0.w * mul, h0, m0, l0);
+    split4x3<false>(v1.x * mul, v1.y * mul, v1.z * mul, v1.w * mul, h1, m1, l1);
     const bool lo = c.g < 2;
     bmh = frag4(lo ? m0.x : h0.x, lo ? m0.y : h0.y, lo ? m1.x : h1.x, lo ? m1.y : h1.y);
     blh = frag4(lo ? l0.x : h0.x, lo ? l0.y : h0.y, lo ? l1.x : h1.x, lo ? l1.y : h1.y);
@@ -183,13 +132,7 @@ __device__ __forceinline__ f32x4 row_prod(const RowFr& f, bf16x8 bmh, bf16x8 blh
     return mm(f.c, bmh, c);
 }
 // transposed fragments of the 32-row block `b32` of an image (A[d][k slot])
-__device__ __forceinline__ bf16x8 tr_pair(const uint16_t* p) {
-    typedef short v8s __attribute__((ext_vector_type(8)));
-    const v4s x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(p));
-    const v4s y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(p + 256));
-    const v8s v = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
+__device__ __forceinline__ bf16x8 tr_pair(const uint16_t* p) { return cat_frag(tr_read(p), tr_read(p + 256)); }
 __device__ __forceinline__ Planes tr_fr(const uint16_t* __restrict__ img, int b32, const LaneN& c) {
     Planes f;
     f.h = tr_pair(img + c.offT + b32 * 512);
@@ -207,25 +150,15 @@ __device__ __forceinline__ float4 stage_ld(const float* __restrict__ base, size_
 }
 __device__ __forceinline__ void stage_st(uint16_t* __restrict__ img, int tid, const float4& v) {
     uint2 h, m, l;
-    split4v(v.x, v.y, v.z, v.w, h, m, l);
+    split4x3<false>(v.x, v.y, v.z, v.w, h, m, l);
     const int off = (tid >> 2) * 16 + 4 * (tid & 3);
     *reinterpret_cast<uint2*>(img + off) = h;
     *reinterpret_cast<uint2*>(img + PLN + off) = m;
     *reinterpret_cast<uint2*>(img + 2 * PLN + off) = l;
 }
-// max / sum over the four lanes (l & 15) + 16 {0, 1, 2, 3} that share a column
-__device__ __forceinline__ float col_max4(float v) {
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float col_sum4(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
 // ------------------------------------------------------------------------------------------ forward
 template <int NB, bool DROP, bool SEED>
-__global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, A6N_OCC) void attn6n_fwd_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);           // [2 buffers][K image | V image]
     uint32_t* htab = reinterpret_cast<uint32_t*>(img0 + 4 * IMGN);   // [2][KT] column hashes of the tile's keys (DROP)
@@ -340,7 +273,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_fwd_kernel(AttnArgs a
                         m_run[n] = SEED ? m_run[n] + m_new : m_new;
                         if (SEED) seed[n] = f32x4{-m_run[n], -m_run[n], -m_run[n], -m_run[n]};
                         o[n] *= alpha;
-                        if (RLT_A6N_2ACC && SEED) o2[n] *= alpha;
+                        if (SEED) o2[n] *= alpha;
                     }
                 }
 #pragma unroll
@@ -357,7 +290,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_fwd_kernel(AttnArgs a
                         }
                     }
                     const Planes pp = split_mx(pe[n][0], pe[n][1], c.sel0, c.sel1);
-                    if (RLT_A6N_2ACC && SEED) mm6_2(vt, pp, o[n], o2[n]);
+                    if (SEED) mm6_2(vt, pp, o[n], o2[n]);
                     else o[n] = mm6(vt, pp, o[n]);                  // O^T[d][q] += V^T P^T
                 }
             }
@@ -374,7 +307,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_fwd_kernel(AttnArgs a
     for (int n = 0; n < NB; ++n) {
         const float l_tot = col_sum4(l_run[n]);
         const int q = row0 + 16 * n + c.l15;
-        if (RLT_A6N_2ACC && SEED) o[n] += o2[n];
+        if (SEED) o[n] += o2[n];
         if (q < B) {
             const float inv = 1.f / l_tot;
             *reinterpret_cast<float4*>(a.o + ((size_t)s * B + q) * E + h * 16 + 4 * c.g) =
@@ -387,7 +320,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_fwd_kernel(AttnArgs a
 // ------------------------------------------------------------------------------------------ dQ
 // Keys beyond B: their K and V rows are staged as zeros, so whatever dS they get multiplies a zero column of K^T.
 template <int NB, bool DROP, bool SEED>
-__global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dq_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, A6N_OCC) void attn6n_bwd_dq_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);           // [2 buffers][K image | V image]
     uint32_t* htab = reinterpret_cast<uint32_t*>(img0 + 4 * IMGN);
@@ -453,21 +386,15 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dq_kernel(AttnArg
 #pragma unroll
                 for (int n = 0; n < NB; ++n) {
                     f32x4 sc[2], dp[2];
-                    if (RLT_A6N_ABL & 4) {
-                        sc[0] = f32x4{lse2[n], del[n], lse2[n], del[n]}; sc[1] = sc[0] * 0.5f; dp[0] = sc[0] + 1.f; dp[1] = sc[1] - 1.f;
-                        asm volatile("" : "+v"(sc[0]), "+v"(sc[1]), "+v"(dp[0]), "+v"(dp[1]));
-                    } else {
                     sc[0] = row_prod(k0, qmh[n], qlh[n], seed_s[n]);                     // S^T[key][q] (- lse[q])
                     sc[1] = row_prod(k1, qmh[n], qlh[n], seed_s[n]);
                     dp[0] = row_prod(v0, dmh[n], dlh[n], seed_d[n]);                     // dP^T[key][q] (- delta[q])
                     dp[1] = row_prod(v1, dmh[n], dlh[n], seed_d[n]);
-                    }
 #pragma unroll
                     for (int kb = 0; kb < 2; ++kb) {
                         const uint32_t hcs[4] = {hc[kb].x, hc[kb].y, hc[kb].z, hc[kb].w};
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            if (RLT_A6N_ABL & 1) continue;
                             const float p = rlt_exp2(SEED ? sc[kb][r] : sc[kb][r] - lse2[n]);
                             float dpr = dp[kb][r];
                             if (DROP) dpr = rlt_keep_rc(hq[n], hcs[r], a.drop_thr) ? dpr * inv_keep : 0.f;
@@ -475,11 +402,9 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dq_kernel(AttnArg
                         }
                     }
                     const Planes ds = split_mx(dp[0], dp[1], c.sel0, c.sel1);
-                    if (RLT_A6N_ABL & 8) { asm volatile("" :: "v"(ds.h), "v"(ds.m), "v"(ds.l)); continue; }
-                    if (RLT_A6N_2ACC && SEED) mm6_2(kt, ds, dq[n], dq2[n]);
+                    if (SEED) mm6_2(kt, ds, dq[n], dq2[n]);
                     else dq[n] = mm6(kt, ds, dq[n]);                                 // dQ^T[d][q] += K^T dS^T
                 }
-                interleave_hint<22 * NB, 2>();
             }
         }
         if (t + 1 < nt) {
@@ -493,7 +418,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dq_kernel(AttnArg
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
         const int q = row0 + 16 * n + c.l15;
-        if (RLT_A6N_2ACC && SEED) dq[n] += dq2[n];
+        if (SEED) dq[n] += dq2[n];
         if (q < B)
             *reinterpret_cast<float4*>(a.dqkv + ((size_t)s * B + q) * ld + h * 16 + 4 * c.g) =
                 make_float4(dq[n][0] * a.scale, dq[n][1] * a.scale, dq[n][2] * a.scale, dq[n][3] * a.scale);
@@ -503,7 +428,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dq_kernel(AttnArg
 // ------------------------------------------------------------------------------------------ dK, dV
 // Queries beyond B: their Q / dO rows are staged as zeros and their lse entry is +inf, so P = dS = 0.
 template <int NB, bool DROP, bool SEED>
-__global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dkv_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, A6N_OCC) void attn6n_bwd_dkv_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);           // [2 buffers][Q image | dO image]
     float* tab0 = reinterpret_cast<float*>(img0 + 4 * IMGN);      // [2 buffers][lse * log2e | delta | row hashes][KT]
@@ -615,13 +540,12 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dkv_kernel(AttnAr
                         }
                     }
                     const Planes pp = split_mx(sc[0], sc[1], c.sel0, c.sel1);
-                    if (RLT_A6N_2ACC && SEED) mm6_2(dt_, pp, dv[n], dv2[n]);
+                    if (SEED) mm6_2(dt_, pp, dv[n], dv2[n]);
                     else dv[n] = mm6(dt_, pp, dv[n]);                                // dV^T[d][key] += dO^T P
                     const Planes ds = split_mx(dp[0], dp[1], c.sel0, c.sel1);
-                    if (RLT_A6N_2ACC && SEED) mm6_2(qt_, ds, dk[n], dk2[n]);
+                    if (SEED) mm6_2(qt_, ds, dk[n], dk2[n]);
                     else dk[n] = mm6(qt_, ds, dk[n]);                                // dK^T[d][key] += Q^T dS
                 }
-                interleave_hint<32 * NB, 2>();
             }
         }
         if (t + 1 < nt) store_tile(buf ^ 1, (t + 1) * KT);
@@ -631,7 +555,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dkv_kernel(AttnAr
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
         const int key = row0 + 16 * n + c.l15;
-        if (RLT_A6N_2ACC && SEED) { dk[n] += dk2[n]; dv[n] += dv2[n]; }
+        if (SEED) { dk[n] += dk2[n]; dv[n] += dv2[n]; }
         if (key < B) {
             float* drow = a.dqkv + ((size_t)s * B + key) * ld + h * 16 + 4 * c.g;
             *reinterpret_cast<float4*>(drow + E) =
@@ -655,9 +579,6 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC) void attn6n_bwd_dkv_kernel(AttnAr
 // runs ACROSS tile boundaries (tiles of 128 rows, double-buffered images, one barrier per tile; every LDS read of a tile is
 // issued before the barrier that ends it) and drains on one extra, empty tile (rows beyond B are staged as zeros - in dK+dV with
 // lse = +inf -, so they add nothing: no masks, no special last tile).  No dropout here (train-mode launches take the kernels above).
-#ifndef RLT_A6N_OCC1
-#define RLT_A6N_OCC1 1       // one wavefront per SIMD, 512 registers (compiled with -mllvm -amdgpu-mfma-vgpr-form: rlt_hip/build.py)
-#endif
 #ifndef RLT_A6N_DQ1_BODY          // (timing experiments compile other generated bodies: tools/gen_attn6n_body.py with GEN_OMIT)
 #define RLT_A6N_DQ1_BODY "attention6n_dq1_body.inc"
 #define RLT_A6N_DKV1_BODY "attention6n_dkv1_body.inc"
@@ -700,7 +621,7 @@ __global__ __launch_bounds__(256) void attn6n_prepare_kernel(const float* __rest
         const float4 t = *reinterpret_cast<const float4*>(base + (size_t)min(row, B - 1) * ld + d0);
         const bool ok = row < B;
         uint2 hh_, mm_, ll_;
-        split4v(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f, hh_, mm_, ll_);
+        split4x3<false>(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f, hh_, mm_, ll_);
         uint16_t* im = rec + r * 16 + d0;
         *reinterpret_cast<uint2*>(im) = hh_;
         *reinterpret_cast<uint2*>(im + PLT) = mm_;
@@ -717,7 +638,7 @@ __global__ __launch_bounds__(256) void attn6n_seed_kernel(const float* __restric
 }
 
 template <bool DKV>
-__global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_bwd1_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, A6N_OCC1) void attn6n_bwd1_kernel(AttnArgs a) {
     constexpr int NB = 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);           // [2 buffers][matrix 0 | matrix 1]: dQ: K, V; dK+dV: Q, dO
@@ -889,23 +810,20 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_bwd1_kernel(AttnArgs
             const int ap = x6_plane_a(k), bp = x6_plane_b(k);
             const int mat = DKV ? (which ? 0 : 1) : 0;          // dQ: K^T; dV: dO^T, dK: Q^T
             const int w = DKV ? which : 0;
-            typedef short v8s __attribute__((ext_vector_type(8)));
             const v4s x = trf[fb][mat][ap][0], y = trf[fb][mat][ap][1];
-            const v8s av = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-            mma_out(k < 5 ? acc2[w][n] : acc[w][n], __builtin_bit_cast(bf16x8, av), plane(which, bp, it));
+            mma_out(k < 5 ? acc2[w][n] : acc[w][n], cat_frag(x, y), plane(which, bp, it));
         };
         auto e_exp = [&](int it, int kb, int r) __attribute__((always_inline)) { sc[it][kb][r] = rlt_exp2(sc[it][kb][r]); };
         auto e_mul = [&](int it, int kb, int r) __attribute__((always_inline)) { dp[it][kb][r] *= sc[it][kb][r]; };
         auto c_pk = [&](int it, int which, int lvl, int j) __attribute__((always_inline)) {
             const f32x4& tile = which ? dp[it][j >> 1] : sc[it][j >> 1];
-            pln[which][lvl][it][j] = pk2n(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
+            pln[which][lvl][it][j] = pk2(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
         };
         auto rd_row = [&](int fb, int mat, int kb, int w, int b32) __attribute__((always_inline)) {
             fr[fb][mat][kb][w] = *reinterpret_cast<const bf16x8*>(Ic + mat * IMGT + offW[w] + (2 * b32 + kb) * 256);
         };
         auto rd_tr = [&](int fb, int mat, int pl, int half, int b32) __attribute__((always_inline)) {
-            trf[fb][mat][pl][half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (v4s __attribute__((address_space(3)))*)(Ic + mat * IMGT + pl * PLT + offT + b32 * 512 + half * 256));
+            trf[fb][mat][pl][half] = tr_read(Ic + mat * IMGT + pl * PLT + offT + b32 * 512 + half * 256);
         };
         auto rd_tab = [&](int fb, int which, int kb, int b32) __attribute__((always_inline)) {
             tabv[fb][which][kb] = *reinterpret_cast<const float4*>(Tc + which * KTN1 + b32 * 32 + kb * 16 + 4 * g);
@@ -949,7 +867,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_bwd1_kernel(AttnArgs
 // raises its flag in a.redo, and a second launch of the two-wavefront kernel (same grid, same block -> rows map) redoes exactly the
 // flagged workgroups with the moving reference (it returns at once everywhere else).  Needs B % 128 == 0 (the drain tile multiplies
 // its row sums by a zero flag; a partly filled tile would need a mask per key), no dropout.
-__global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs a) {
     constexpr int NB = 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     uint16_t* img0 = reinterpret_cast<uint16_t*>(smem);           // [2 buffers][K image | V image]
@@ -1071,10 +989,8 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs
         };
         auto m_o = [&](int it, int n, int which, int k, int fb) __attribute__((always_inline)) {
             const int ap = x6_plane_a(k), bp = x6_plane_b(k);
-            typedef short v8s __attribute__((ext_vector_type(8)));
             const v4s x = trf[fb][1][ap][0], y = trf[fb][1][ap][1];
-            const v8s av = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-            mma_out(k < 5 ? acc2[n] : acc[n], __builtin_bit_cast(bf16x8, av), plane(0, bp, it));
+            mma_out(k < 5 ? acc2[n] : acc[n], cat_frag(x, y), plane(0, bp, it));
         };
         auto e_exp = [&](int it, int kb, int r) __attribute__((always_inline)) { sc[it][kb][r] = rlt_exp2(sc[it][kb][r]); };
         // (chunks of the previous tile's last items: in the first body there is no previous tile - the ring holds zeros - and the weight must be 0, not exp2(0))
@@ -1083,14 +999,13 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs
         auto e_sum_p = [&](int it, int n, int kb, int r) __attribute__((always_inline)) { l_run[n] += sc[it][kb][r]; };
         auto c_pk = [&](int it, int which, int lvl, int j) __attribute__((always_inline)) {
             const f32x4& tile = sc[it][j >> 1];
-            pln[0][lvl][it][j] = pk2n(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
+            pln[0][lvl][it][j] = pk2(tile[2 * (j & 1)], tile[2 * (j & 1) + 1]);
         };
         auto rd_row = [&](int fb, int mat, int kb, int w, int b32) __attribute__((always_inline)) {
             fr[fb][0][kb][w] = *reinterpret_cast<const bf16x8*>(Ic + offW[w] + (2 * b32 + kb) * 256);
         };
         auto rd_tr = [&](int fb, int mat, int pl, int half, int b32) __attribute__((always_inline)) {
-            trf[fb][1][pl][half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (v4s __attribute__((address_space(3)))*)(Ic + IMGT + pl * PLT + offT + b32 * 512 + half * 256));
+            trf[fb][1][pl][half] = tr_read(Ic + IMGT + pl * PLT + offT + b32 * 512 + half * 256);
         };
         auto st_dma = [&](int j) __attribute__((always_inline)) { dma(j, t_next, In); };
 #include "attention6n_fwd1_body.inc"
@@ -1123,7 +1038,7 @@ __global__ __launch_bounds__(256, RLT_A6N_OCC1) void attn6n_fwd1_kernel(AttnArgs
 
 template <bool DROP>
 int launch6n(int kernel, int which, const AttnArgs& a, hipStream_t st) {
-    constexpr int NB = RLT_A6N_NB, NBK = RLT_A6N_NBK;
+    constexpr int NB = A6N_NB, NBK = A6N_NBK;
     const size_t shm = (size_t)4 * IMGN * sizeof(uint16_t) + (which == 1 ? 2 * 3 * KT * sizeof(float) : 2 * KT * sizeof(uint32_t));
     const dim3 gq(a.S * a.H * rlt_cdiv(a.B, 64 * NB)), gk(a.S * a.H * rlt_cdiv(a.B, 64 * NBK));
     if (kernel == RLT_ATTN_X6N_PIPE) {        // the one-wavefront pipelined kernels: no dropout, 512 lists and more, images in a.img

@@ -49,6 +49,7 @@ static inline bool rlt_precision_arg_ok(int p) {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// (the bf16 vector types, the bf16x3 / bf16x6 split primitives and their MFMA sequences: split6.h)
 
 // ---- wavefront (64 lanes) reductions / scans ------------------------------------------------
 // raw v_exp_f32 (2^x, 1 ulp): unlike exp2f() no denormal-range rescue sequence (6 extra VALU ops); results

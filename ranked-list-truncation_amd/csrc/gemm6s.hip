@@ -14,11 +14,11 @@
 // One barrier per block.  Row bounds are buffer bounds (rows past M are never loaded or stored).
 #include "common.h"
 #include "gemm6s.h"
+#include "split6.h"
 #include <type_traits>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // KS = K / 32 k-steps: 8 (K = 256: AttnCut's d_model) or 4 (K = 128: Choopy's; the whole l plane of the panel fits the VGPRs, no LDS part)
@@ -29,27 +29,6 @@ template <int KS> constexpr int gs_wl() { return KS > 4 ? 4 * 4 * (KS - 4) * 64 
 template <int KS> constexpr size_t gs_lds() { return (size_t)2 * gs_buf<KS>() + gs_wl<KS>(); }
 static_assert(gs_lds<8>() == 160 * 1024, "the K = 256 streaming product fills LDS exactly");
 
-__device__ __forceinline__ uint32_t pk2s(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ float bfs_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bfs_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-__device__ __forceinline__ void split4s(float a, float b, float c, float d, uint2& hi, uint2& mid, uint2& lo) {
-    hi.x = pk2s(a, b);
-    hi.y = pk2s(c, d);
-    asm("" : "+v"(hi.x), "+v"(hi.y));
-    const float ra = a - bfs_lo(hi.x), rb = b - bfs_hi(hi.x), rc = c - bfs_lo(hi.y), rd = d - bfs_hi(hi.y);
-    mid.x = pk2s(ra, rb);
-    mid.y = pk2s(rc, rd);
-    asm("" : "+v"(mid.x), "+v"(mid.y));
-    lo.x = pk2s(ra - bfs_lo(mid.x), rb - bfs_hi(mid.x));
-    lo.y = pk2s(rc - bfs_lo(mid.y), rd - bfs_hi(mid.y));
-}
-__device__ __forceinline__ bf16x8 frag8s(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    return __builtin_bit_cast(bf16x8, make_uint4(a, b, c, d));
-}
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_s(const void* p, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
@@ -95,15 +74,15 @@ __global__ __launch_bounds__(256, 1) void gemm6s_kernel(Gemm6sArgs g) {
                     for (int j = 0; j < 8; ++j) v[j] = wp[(size_t)(32 * ks + j) * g.ldb];
                 }
                 uint2 h0, m0, l0, h1, m1, l1;
-                split4s(v[0], v[1], v[2], v[3], h0, m0, l0);
-                split4s(v[4], v[5], v[6], v[7], h1, m1, l1);
+                split4x3<true>(v[0], v[1], v[2], v[3], h0, m0, l0);
+                split4x3<true>(v[4], v[5], v[6], v[7], h1, m1, l1);
                 if (pass == 0) {
-                    wh[cb][ks] = frag8s(h0.x, h0.y, h1.x, h1.y);
-                    wm[cb][ks] = frag8s(m0.x, m0.y, m1.x, m1.y);
+                    wh[cb][ks] = frag4(h0.x, h0.y, h1.x, h1.y);
+                    wm[cb][ks] = frag4(m0.x, m0.y, m1.x, m1.y);
                     asm volatile("" : "+a"(wh[cb][ks]), "+a"(wm[cb][ks]) : : "memory");
                     if (KS > 4 && ks >= 4) wl_s[((w * 4 + cb) * (KS - 4) + (ks - 4)) * 64 + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
                 } else {
-                    wlv[cb][ks] = frag8s(l0.x, l0.y, l1.x, l1.y);
+                    wlv[cb][ks] = frag4(l0.x, l0.y, l1.x, l1.y);
                     asm volatile("" : "+v"(wlv[cb][ks]) : : "memory");
                 }
             }
@@ -164,24 +143,24 @@ __global__ __launch_bounds__(256, 1) void gemm6s_kernel(Gemm6sArgs g) {
 #pragma unroll
     for (int i = 0; i < 2 * NI; ++i) xs[i] = z4;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag8s(0u, 0u, 0u, 0u);
+    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag4(0u, 0u, 0u, 0u);
 #pragma unroll
-    for (int i = 0; i < NCB; ++i) lfr[i] = frag8s(0u, 0u, 0u, 0u);
+    for (int i = 0; i < NCB; ++i) lfr[i] = frag4(0u, 0u, 0u, 0u);
     sph = spm = spl = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) bw[cb] = u32x4{0u, 0u, 0u, 0u};
     auto load_x = [&](int i4, int part, __amdgpu_buffer_rsrc_t r) __attribute__((always_inline)) {
         xs[2 * i4 + part] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_a + 16u * part, (uint32_t)(RPP * i4) * g.lda * 4u, 0));
     };
-    auto split_x = [&](int i4, int part) __attribute__((always_inline)) {         // pieces of split4s on xs[2 i4], xs[2 i4 + 1] (residuals in place)
+    auto split_x = [&](int i4, int part) __attribute__((always_inline)) {         // pieces of split4x3 on xs[2 i4], xs[2 i4 + 1] (residuals in place)
         f32x4 &a = xs[2 * i4], &b = xs[2 * i4 + 1];
-        if (part == 0) { sph = make_uint4(pk2s(a[0], a[1]), pk2s(a[2], a[3]), pk2s(b[0], b[1]), pk2s(b[2], b[3])); asm("" : "+v"(sph.x), "+v"(sph.y), "+v"(sph.z), "+v"(sph.w)); }
-        if (part == 1) { a[0] -= bfs_lo(sph.x); a[1] -= bfs_hi(sph.x); a[2] -= bfs_lo(sph.y); a[3] -= bfs_hi(sph.y); }
-        if (part == 2) { b[0] -= bfs_lo(sph.z); b[1] -= bfs_hi(sph.z); b[2] -= bfs_lo(sph.w); b[3] -= bfs_hi(sph.w); }
-        if (part == 3) { spm = make_uint4(pk2s(a[0], a[1]), pk2s(a[2], a[3]), pk2s(b[0], b[1]), pk2s(b[2], b[3])); asm("" : "+v"(spm.x), "+v"(spm.y), "+v"(spm.z), "+v"(spm.w)); }
-        if (part == 4) { a[0] -= bfs_lo(spm.x); a[1] -= bfs_hi(spm.x); a[2] -= bfs_lo(spm.y); a[3] -= bfs_hi(spm.y); }
-        if (part == 5) { b[0] -= bfs_lo(spm.z); b[1] -= bfs_hi(spm.z); b[2] -= bfs_lo(spm.w); b[3] -= bfs_hi(spm.w); }
-        if (part == 6) spl = make_uint4(pk2s(a[0], a[1]), pk2s(a[2], a[3]), pk2s(b[0], b[1]), pk2s(b[2], b[3]));
+        if (part == 0) { sph = make_uint4(pk2(a[0], a[1]), pk2(a[2], a[3]), pk2(b[0], b[1]), pk2(b[2], b[3])); asm("" : "+v"(sph.x), "+v"(sph.y), "+v"(sph.z), "+v"(sph.w)); }
+        if (part == 1) { a[0] -= lo16(sph.x); a[1] -= hi16(sph.x); a[2] -= lo16(sph.y); a[3] -= hi16(sph.y); }
+        if (part == 2) { b[0] -= lo16(sph.z); b[1] -= hi16(sph.z); b[2] -= lo16(sph.w); b[3] -= hi16(sph.w); }
+        if (part == 3) { spm = make_uint4(pk2(a[0], a[1]), pk2(a[2], a[3]), pk2(b[0], b[1]), pk2(b[2], b[3])); asm("" : "+v"(spm.x), "+v"(spm.y), "+v"(spm.z), "+v"(spm.w)); }
+        if (part == 4) { a[0] -= lo16(spm.x); a[1] -= hi16(spm.x); a[2] -= lo16(spm.y); a[3] -= hi16(spm.y); }
+        if (part == 5) { b[0] -= lo16(spm.z); b[1] -= hi16(spm.z); b[2] -= lo16(spm.w); b[3] -= hi16(spm.w); }
+        if (part == 6) spl = make_uint4(pk2(a[0], a[1]), pk2(a[2], a[3]), pk2(b[0], b[1]), pk2(b[2], b[3]));
     };
     auto write_x = [&](int buf, int i4, int pl) __attribute__((always_inline)) {
         *reinterpret_cast<uint4*>(sm6s + buf * GS_BUF + pl * GS_PLANE + wro[i4]) = pl == 0 ? sph : pl == 1 ? spm : spl;

@@ -21,6 +21,7 @@
 // plain GEMMs / column sums on it (position-major layout makes h_{t-1} a row offset of B).
 #include "common.h"
 #include "lstm_common.h"
+#include "split6.h"
 #include <stdlib.h>
 
 namespace {
@@ -261,36 +262,8 @@ __global__ __launch_bounds__(1024) void bilstm_bwd_kernel(float* __restrict__ ga
 // Split-bf16 ("bf16x3") variants: the recurrent products h W_hh^T and W_hh^T dA on v_mfma_f32_32x32x16_bf16 with
 // every operand split into bf16 hi + lo (3 products, fp32 accumulate); W_hh fragments still live in registers
 // (64 VGPRs), h_{t-1} is exchanged through LDS already split.  Gate nonlinearities use v_exp/v_rcp forms.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int LDH3 = 136;      // bf16 elements per row of the h tile images (272 B)
 
-__device__ __forceinline__ uint32_t pk2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ void split4(float a, float b, float c, float d, uint2& hi, uint2& lo) {
-    hi.x = pk2(a, b);
-    hi.y = pk2(c, d);
-    // opaque to the optimiser: otherwise hipcc re-derives the low element's bf16 with a second v_cvt_pk (x, 0) instead
-    // of shifting the packed pair (one extra VALU instruction per two elements)
-    asm("" : "+v"(hi.x), "+v"(hi.y));
-    lo.x = pk2(a - __builtin_bit_cast(float, hi.x << 16), b - __builtin_bit_cast(float, hi.x & 0xffff0000u));
-    lo.y = pk2(c - __builtin_bit_cast(float, hi.y << 16), d - __builtin_bit_cast(float, hi.y & 0xffff0000u));
-}
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
-    uint2 h0, l0, h1, l1;
-    split4(x[0], x[1], x[2], x[3], h0, l0);
-    split4(x[4], x[5], x[6], x[7], h1, l1);
-    hi = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-    lo = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-}
-__device__ __forceinline__ f32x16 mfma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-    return c;
-}
 // sigmoid / tanh on the hardware exp2 + rcp (abs error ~1e-7, far inside the 1e-4 parity bound)
 __device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + rlt_exp2(-1.4426950408889634f * x)); }
 __device__ __forceinline__ float ftanh(float x) { return 2.f * fsigmoid(2.f * x) - 1.f; }
@@ -517,36 +490,6 @@ __global__ __launch_bounds__(512) void bilstm3_bwd8_kernel(float* __restrict__ g
 // fragments (W_ih columns, the bias sum, zeros; all three planes in registers) meet B = (x0, x1, x2, 1, 0...) - exact like
 // every other product of the mode; the pre-activations never exist in memory.  Gate nonlinearities: hardware exp2 / rcp forms
 // (abs error ~1e-7, measured against the libm forms of the f32 kernel in every fp32-tolerance test of the suite).
-__device__ __forceinline__ void split4x3_(float a, float b, float c, float d, uint2& hi, uint2& mid, uint2& lo) {
-    hi.x = pk2(a, b);
-    hi.y = pk2(c, d);
-    asm("" : "+v"(hi.x), "+v"(hi.y));          // keep the packed pair, do not re-convert (see split4)
-    const float ra = a - __builtin_bit_cast(float, hi.x << 16), rb = b - __builtin_bit_cast(float, hi.x & 0xffff0000u);
-    const float rc = c - __builtin_bit_cast(float, hi.y << 16), rd = d - __builtin_bit_cast(float, hi.y & 0xffff0000u);
-    mid.x = pk2(ra, rb);
-    mid.y = pk2(rc, rd);
-    asm("" : "+v"(mid.x), "+v"(mid.y));
-    lo.x = pk2(ra - __builtin_bit_cast(float, mid.x << 16), rb - __builtin_bit_cast(float, mid.x & 0xffff0000u));
-    lo.y = pk2(rc - __builtin_bit_cast(float, mid.y << 16), rd - __builtin_bit_cast(float, mid.y & 0xffff0000u));
-}
-__device__ __forceinline__ void split8x3(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    uint2 h0, m0, l0, h1, m1, l1;
-    split4x3_(x[0], x[1], x[2], x[3], h0, m0, l0);
-    split4x3_(x[4], x[5], x[6], x[7], h1, m1, l1);
-    h = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-    m = __builtin_bit_cast(bf16x8, make_uint4(m0.x, m0.y, m1.x, m1.y));
-    l = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-}
-// the six products, smallest terms first
-__device__ __forceinline__ f32x16 mfma6(bf16x8 ah, bf16x8 am, bf16x8 al, bf16x8 bh, bf16x8 bm, bf16x8 bl, f32x16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-    return c;
-}
 constexpr int WL6_BYTES = 8 * 2 * 8 * 64 * 16;          // l plane of W_hh in fragment order
 constexpr int HX6_PLANE = LISTS * 256;                   // one plane of the h tile: 32 lists x 128 bf16
 constexpr size_t LSTM6_LDS = (size_t)WL6_BYTES + 3 * HX6_PLANE;
@@ -582,7 +525,7 @@ __global__ __launch_bounds__(512) void bilstm6_fwd_kernel(float* __restrict__ ga
             const float4 v1 = *reinterpret_cast<const float4*>(wp + 16 * ks + 4);
             const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
             bf16x8 wl;
-            split8x3(x, wh[blk][ks], wm[blk][ks], wl);
+            split8x3<true>(x, wh[blk][ks], wm[blk][ks], wl);
             wl_s[((w * 2 + blk) * 8 + ks) * 64 + lane] = __builtin_bit_cast(uint4, wl);
         }
         if (XIN) {
@@ -590,7 +533,7 @@ __global__ __launch_bounds__(512) void bilstm6_fwd_kernel(float* __restrict__ ga
             const bool lo_half = hh == 0;
             const float x[8] = {lo_half ? wr[0] : 0.f, (lo_half && xi.I > 1) ? wr[1] : 0.f, (lo_half && xi.I > 2) ? wr[2] : 0.f,
                                 lo_half ? xi.b_ih[dir][row] + xi.b_hh[dir][row] : 0.f, 0.f, 0.f, 0.f, 0.f};
-            split8x3(x, wxh[blk], wxm[blk], wxl[blk]);
+            split8x3<true>(x, wxh[blk], wxm[blk], wxl[blk]);
         }
     }
     for (int i = tid; i < 3 * HX6_PLANE / 16; i += 512) reinterpret_cast<uint4*>(hx)[i] = make_uint4(0u, 0u, 0u, 0u);   // h_0 = 0
@@ -680,7 +623,7 @@ __global__ __launch_bounds__(512) void bilstm6_fwd_kernel(float* __restrict__ ga
             const bool lo_half = hh == 0;
             const float x[8] = {lo_half ? xv[0] : 0.f, lo_half ? xv[1] : 0.f, lo_half ? xv[2] : 0.f, lo_half ? 1.f : 0.f, 0.f, 0.f, 0.f, 0.f};
             bf16x8 xh, xm, xl;
-            split8x3(x, xh, xm, xl);
+            split8x3<true>(x, xh, xm, xl);
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) acc[blk] = mfma6(wxh[blk], wxm[blk], wxl[blk], xh, xm, xl, acc[blk]);
         }
@@ -716,7 +659,7 @@ __global__ __launch_bounds__(512) void bilstm6_fwd_kernel(float* __restrict__ ga
                     make_float4(hnew[blk][0], hnew[blk][1], hnew[blk][2], hnew[blk][3]);
             }
             uint2 h2, m2, l2;
-            split4x3_(hnew[blk][0], hnew[blk][1], hnew[blk][2], hnew[blk][3], h2, m2, l2);
+            split4x3<true>(hnew[blk][0], hnew[blk][1], hnew[blk][2], hnew[blk][3], h2, m2, l2);
             uint8_t* dst = hx + l31 * 256 + (((2 * w + blk) ^ sw) * 16) + 8 * hh;
             *reinterpret_cast<uint2*>(dst) = h2;
             *reinterpret_cast<uint2*>(dst + HX6_PLANE) = m2;

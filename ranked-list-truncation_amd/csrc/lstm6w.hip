@@ -20,13 +20,13 @@
 // block - the 24 (plane of W_ih, plane of x) pairs of the six products of the four values (x0, x1, x2, 1) fill the 32 k slots.
 #include "common.h"
 #include "lstm_common.h"
+#include "split6.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
 constexpr int HID = 128;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int W6_WL = 4 * 8 * 4 * 64 * 16;       // l plane of W_hh in fragment order: [wavefront][row block][k-step][lane] x 16 B
@@ -36,39 +36,11 @@ constexpr int W6_HALF = 3 * W6_PLANE;
 constexpr size_t W6_LDS = (size_t)W6_WL + 2 * W6_HALF;
 constexpr float LOG2E = 1.4426950408889634f;
 
-__device__ __forceinline__ uint32_t pk2w(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    v2 t = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, t);
-}
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// exact three-way split of four values: x = h + m + l, 8 + 8 + 8 significand bits
-__device__ __forceinline__ void split4w(float a, float b, float c, float d, uint2& hi, uint2& mid, uint2& lo) {
-    hi.x = pk2w(a, b);
-    hi.y = pk2w(c, d);
-    asm("" : "+v"(hi.x), "+v"(hi.y));          // keep the packed pair, do not re-convert
-    const float ra = a - bf_lo(hi.x), rb = b - bf_hi(hi.x), rc = c - bf_lo(hi.y), rd = d - bf_hi(hi.y);
-    mid.x = pk2w(ra, rb);
-    mid.y = pk2w(rc, rd);
-    asm("" : "+v"(mid.x), "+v"(mid.y));
-    lo.x = pk2w(ra - bf_lo(mid.x), rb - bf_hi(mid.x));
-    lo.y = pk2w(rc - bf_lo(mid.y), rd - bf_hi(mid.y));
-}
-__device__ __forceinline__ bf16x8 frag8(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    return __builtin_bit_cast(bf16x8, make_uint4(a, b, c, d));
-}
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
 
 enum { TICK_FULL = 0, TICK_CHAIN = 1, TICK_ELEM = 2 };
-#ifndef RLT_W6_STAGGER
-#define RLT_W6_STAGGER 0    // experiment: wavefront w starts a tick 16 * w * RLT_W6_STAGGER cycles late (memory / LDS instructions of the four out of step)
-#endif
-#ifndef RLT_W6_ABL
-#define RLT_W6_ABL 0        // timing ablations (tools/build_variant.py; wrong results): 1 no stores, 2 no pre-activation loads, 4 no MFMAs, 8 no exp / rcp
-#endif
 
 // SINGLE (batches that give every CU at most one 16-list half: B <= 16 x 128 per direction): a workgroup owns ONE half and a step is
 // chain tick, then element-wise tick of the SAME half (nothing to overlap, but a step is one chain long instead of two: the latency
@@ -96,10 +68,10 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
                 const float4 v0 = *reinterpret_cast<const float4*>(wp + 32 * ks);
                 const float4 v1 = *reinterpret_cast<const float4*>(wp + 32 * ks + 4);
                 uint2 h0, m0, l0, h1, m1, l1;
-                split4w(v0.x, v0.y, v0.z, v0.w, h0, m0, l0);
-                split4w(v1.x, v1.y, v1.z, v1.w, h1, m1, l1);
-                wh[rb][ks] = frag8(h0.x, h0.y, h1.x, h1.y);
-                wm[rb][ks] = frag8(m0.x, m0.y, m1.x, m1.y);
+                split4x3<true>(v0.x, v0.y, v0.z, v0.w, h0, m0, l0);
+                split4x3<true>(v1.x, v1.y, v1.z, v1.w, h1, m1, l1);
+                wh[rb][ks] = frag4(h0.x, h0.y, h1.x, h1.y);
+                wm[rb][ks] = frag4(m0.x, m0.y, m1.x, m1.y);
                 wl_s[((w * 8 + rb) * 4 + ks) * 64 + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
                 asm volatile("" : "+a"(wh[rb][ks]), "+a"(wm[rb][ks]));      // into their AGPRs at once: no MFMA of any tick sees a register move
             }
@@ -109,12 +81,12 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
                 //                 {xh, xh, xh, -} / {xm, xl, xm, -}: all six products of the split (see XB below)
                 const float* wr = xi.w_ih[dir] + (size_t)row * xi.I;
                 uint2 h0, m0, l0;
-                split4w(wr[0], xi.I > 1 ? wr[1] : 0.f, xi.I > 2 ? wr[2] : 0.f, xi.b_ih[dir][row] + xi.b_hh[dir][row], h0, m0, l0);
+                split4x3<true>(wr[0], xi.I > 1 ? wr[1] : 0.f, xi.I > 2 ? wr[2] : 0.f, xi.b_ih[dir][row] + xi.b_hh[dir][row], h0, m0, l0);
                 const uint2 z = make_uint2(0u, 0u);
                 const uint2 s0 = q == 0 ? h0 : q == 1 ? m0 : q == 2 ? l0 : z, s1 = q == 0 ? h0 : q == 1 ? h0 : q == 2 ? m0 : z;
-                wx[rb] = frag8(s0.x, s0.y, s1.x, s1.y);
+                wx[rb] = frag4(s0.x, s0.y, s1.x, s1.y);
             } else {
-                wx[rb] = frag8(0u, 0u, 0u, 0u);
+                wx[rb] = frag4(0u, 0u, 0u, 0u);
             }
         }
     }
@@ -146,12 +118,12 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
 #pragma unroll
         for (int rb = 0; rb < 8; ++rb) { acc[hf][rb] = z4; gin[hf][rb] = z4; }
         cst[hf][0] = z4; cst[hf][1] = z4;
-        xb[hf] = frag8(0u, 0u, 0u, 0u);
+        xb[hf] = frag4(0u, 0u, 0u, 0u);
         xv[hf][0] = xv[hf][1] = xv[hf][2] = 0.f;
     }
     sp[0] = sp[1] = sp[2] = make_uint2(0u, 0u);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag8(0u, 0u, 0u, 0u);
+    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag4(0u, 0u, 0u, 0u);
     // (all three x columns are fetched whatever I is - a row's neighbours or, past the end, the buffer bound's zero - and the
     //  columns beyond I replaced by zero with a select: no branch in the tick body)
     auto load_x3 = [&](int hf, __amdgpu_buffer_rsrc_t r) __attribute__((always_inline)) {
@@ -165,10 +137,10 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
     auto load_x = [&](int hf, int t) __attribute__((always_inline)) { load_x3(hf, rs_x(t)); };
     auto make_xb = [&](int hf) __attribute__((always_inline)) {
         uint2 xh, xm, xl;
-        split4w(xv[hf][0], xi.I > 1 ? xv[hf][1] : 0.f, xi.I > 2 ? xv[hf][2] : 0.f, 1.f, xh, xm, xl);
+        split4x3<true>(xv[hf][0], xi.I > 1 ? xv[hf][1] : 0.f, xi.I > 2 ? xv[hf][2] : 0.f, 1.f, xh, xm, xl);
         const uint2 z = make_uint2(0u, 0u);
         const uint2 s0 = q < 3 ? xh : z, s1 = q == 1 ? xl : q == 3 ? z : xm;
-        xb[hf] = frag8(s0.x, s0.y, s1.x, s1.y);
+        xb[hf] = frag4(s0.x, s0.y, s1.x, s1.y);
     };
     if (XIN) {
 #pragma unroll
@@ -215,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
             if (CH) lfr[j] = *reinterpret_cast<const bf16x8*>(wlrd + 1024 * (4 * rb + ks));
         };
         auto MF = [&](int rb, int ks, int p, int first) __attribute__((always_inline)) {
-            if (!CH || (RLT_W6_ABL & 4)) return;
+            if (!CH) return;
             const int bp = p == 2 ? 2 : (p == 0 || p == 4) ? 1 : 0;              // operand plane: m, h, l, h, m, h
             const bf16x8 bv = bfr[ks & 1][bp];
             f32x4& d = acc[X][rb];
@@ -237,20 +209,20 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
         // ---- element-wise side (in place on half Y's accumulators: i, f, g, o of block ub in acc[Y][4 ub + 0..3]) ----
         auto EA = [&](int u, int g) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + g] += gin[Y][4 * u + g]; };
         auto LG = [&](int u, int g) __attribute__((always_inline)) {
-            if (EL && !(RLT_W6_ABL & 2)) gin[Y][4 * u + g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rgn, voff_g[Y] + 512 * g + 64 * u, 0, 0));
+            if (EL) gin[Y][4 * u + g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rgn, voff_g[Y] + 512 * g + 64 * u, 0, 0));
         };
         auto ES = [&](int u, int g) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + g] *= (g == 2 ? -2.f * LOG2E : -LOG2E); };
-        auto EX = [&](int u, int g, int r) __attribute__((always_inline)) { if (EL && !(RLT_W6_ABL & 8)) acc[Y][4 * u + g][r] = rlt_exp2(acc[Y][4 * u + g][r]); };
+        auto EX = [&](int u, int g, int r) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + g][r] = rlt_exp2(acc[Y][4 * u + g][r]); };
         auto E1 = [&](int u, int g) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + g] += 1.f; };
-        auto ER = [&](int u, int g, int r) __attribute__((always_inline)) { if (EL && !(RLT_W6_ABL & 8)) acc[Y][4 * u + g][r] = __builtin_amdgcn_rcpf(acc[Y][4 * u + g][r]); };
+        auto ER = [&](int u, int g, int r) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + g][r] = __builtin_amdgcn_rcpf(acc[Y][4 * u + g][r]); };
         auto EG = [&](int u) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + 2] = 2.f * acc[Y][4 * u + 2] - 1.f; };
         auto SG = [&](int u, int g) __attribute__((always_inline)) {
-            if (EL && !(RLT_W6_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[Y][4 * u + g]), rg, voff_g[Y] + 512 * g + 64 * u, 0, 0);
+            if (EL) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[Y][4 * u + g]), rg, voff_g[Y] + 512 * g + 64 * u, 0, 0);
         };
         auto EC1 = [&](int u) __attribute__((always_inline)) { if (EL) cst[Y][u] *= acc[Y][4 * u + 1]; };
         auto EC2 = [&](int u) __attribute__((always_inline)) { if (EL) cst[Y][u] += acc[Y][4 * u] * acc[Y][4 * u + 2]; };
         auto SC = [&](int u) __attribute__((always_inline)) {
-            if (EL && !(RLT_W6_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cst[Y][u]), rc, voff_h[Y] + 64 * u, 0, 0);
+            if (EL) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cst[Y][u]), rc, voff_h[Y] + 64 * u, 0, 0);
         };
         // tanh(c) in the registers of the i gate, h in those of the f gate, split residuals in those of the g gate
         auto ET = [&](int u) __attribute__((always_inline)) { if (EL) acc[Y][4 * u] = cst[Y][u] * (-2.f * LOG2E); };
@@ -260,19 +232,19 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
         auto EH1 = [&](int u) __attribute__((always_inline)) { if (EL) acc[Y][4 * u] = 2.f * acc[Y][4 * u] - 1.f; };
         auto EH2 = [&](int u) __attribute__((always_inline)) { if (EL) acc[Y][4 * u + 1] = acc[Y][4 * u + 3] * acc[Y][4 * u]; };
         auto SH = [&](int u) __attribute__((always_inline)) {
-            if (EL && !(RLT_W6_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[Y][4 * u + 1]), rh, voff_h[Y] + 64 * u, 0, 0);
+            if (EL) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[Y][4 * u + 1]), rh, voff_h[Y] + 64 * u, 0, 0);
         };
         auto SP = [&](int u, int part) __attribute__((always_inline)) {
             if (!EL) return;
             const f32x4& hv = acc[Y][4 * u + 1];
             f32x4& rs = acc[Y][4 * u + 2];
-            if (part == 0) { sp[0].x = pk2w(hv[0], hv[1]); sp[0].y = pk2w(hv[2], hv[3]); asm("" : "+v"(sp[0].x), "+v"(sp[0].y)); }
-            if (part == 1) { rs[0] = hv[0] - bf_lo(sp[0].x); rs[1] = hv[1] - bf_hi(sp[0].x); }
-            if (part == 2) { rs[2] = hv[2] - bf_lo(sp[0].y); rs[3] = hv[3] - bf_hi(sp[0].y); }
-            if (part == 3) { sp[1].x = pk2w(rs[0], rs[1]); sp[1].y = pk2w(rs[2], rs[3]); asm("" : "+v"(sp[1].x), "+v"(sp[1].y)); }
-            if (part == 4) { rs[0] -= bf_lo(sp[1].x); rs[1] -= bf_hi(sp[1].x); }
-            if (part == 5) { rs[2] -= bf_lo(sp[1].y); rs[3] -= bf_hi(sp[1].y); }
-            if (part == 6) { sp[2].x = pk2w(rs[0], rs[1]); sp[2].y = pk2w(rs[2], rs[3]); }
+            if (part == 0) { sp[0].x = pk2(hv[0], hv[1]); sp[0].y = pk2(hv[2], hv[3]); asm("" : "+v"(sp[0].x), "+v"(sp[0].y)); }
+            if (part == 1) { rs[0] = hv[0] - lo16(sp[0].x); rs[1] = hv[1] - hi16(sp[0].x); }
+            if (part == 2) { rs[2] = hv[2] - lo16(sp[0].y); rs[3] = hv[3] - hi16(sp[0].y); }
+            if (part == 3) { sp[1].x = pk2(rs[0], rs[1]); sp[1].y = pk2(rs[2], rs[3]); asm("" : "+v"(sp[1].x), "+v"(sp[1].y)); }
+            if (part == 4) { rs[0] -= lo16(sp[1].x); rs[1] -= hi16(sp[1].x); }
+            if (part == 5) { rs[2] -= lo16(sp[1].y); rs[3] -= hi16(sp[1].y); }
+            if (part == 6) { sp[2].x = pk2(rs[0], rs[1]); sp[2].y = pk2(rs[2], rs[3]); }
         };
         auto LW = [&](int u, int pl) __attribute__((always_inline)) {
             if (EL) *reinterpret_cast<uint2*>(hwr[Y] + pl * W6_PLANE + 32 * u) = sp[pl];
@@ -297,7 +269,6 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_fwd_kernel(float* __restrict_
 #include "lstm6w_fwd_body.inc"
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        for (int i = 0; i < w * RLT_W6_STAGGER; ++i) asm volatile("s_nop 15");
     };
     const std::integral_constant<int, 0> H0;
     const std::integral_constant<int, 1> H1;
@@ -377,10 +348,10 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = wp[(size_t)((j & 3) * HID + 8 * ks + (j >> 2)) * HID];
                 uint2 h0, m0, l0, h1, m1, l1;
-                split4w(v[0], v[1], v[2], v[3], h0, m0, l0);
-                split4w(v[4], v[5], v[6], v[7], h1, m1, l1);
-                wh[ub][ks] = frag8(h0.x, h0.y, h1.x, h1.y);
-                wm[ub][ks] = frag8(m0.x, m0.y, m1.x, m1.y);
+                split4x3<true>(v[0], v[1], v[2], v[3], h0, m0, l0);
+                split4x3<true>(v[4], v[5], v[6], v[7], h1, m1, l1);
+                wh[ub][ks] = frag4(h0.x, h0.y, h1.x, h1.y);
+                wm[ub][ks] = frag4(m0.x, m0.y, m1.x, m1.y);
                 asm volatile("" : "+a"(wh[ub][ks]), "+a"(wm[ub][ks]) : : "memory");     // ("memory": the loads of later fragments stay behind)
                 if (ks >= 8) wl_s[((w * 2 + ub) * 8 + (ks - 8)) * 64 + lane] = make_uint4(l0.x, l0.y, l1.x, l1.y);
             }
@@ -397,9 +368,9 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = wp[(size_t)((j & 3) * HID + 8 * ks + (j >> 2)) * HID];
                 uint2 h0, m0, l0, h1, m1, l1;
-                split4w(v[0], v[1], v[2], v[3], h0, m0, l0);
-                split4w(v[4], v[5], v[6], v[7], h1, m1, l1);
-                wlv[ub][ks] = frag8(l0.x, l0.y, l1.x, l1.y);
+                split4x3<true>(v[0], v[1], v[2], v[3], h0, m0, l0);
+                split4x3<true>(v[4], v[5], v[6], v[7], h1, m1, l1);
+                wlv[ub][ks] = frag4(l0.x, l0.y, l1.x, l1.y);
                 asm volatile("" : "+v"(wlv[ub][ks]) : : "memory");
             }
         }
@@ -446,8 +417,8 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
 #pragma unroll
     for (int i = 0; i < 4; ++i) h4[i] = m4[i] = l4[i] = 0u;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag8(0u, 0u, 0u, 0u);
-    lfr[0] = lfr[1] = frag8(0u, 0u, 0u, 0u);
+    for (int i = 0; i < 6; ++i) (&bfr[0][0])[i] = frag4(0u, 0u, 0u, 0u);
+    lfr[0] = lfr[1] = frag4(0u, 0u, 0u, 0u);
     {
         const __amdgpu_buffer_rsrc_t rc = rsrc_of(cst + (size_t)pos_of(0) * B * (2 * HID), (uint32_t)B * 1024u);
 #pragma unroll
@@ -487,7 +458,7 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
             if (CH) lfr[ub] = *reinterpret_cast<const bf16x8*>(wlrd + 1024 * (8 * ub + ks - 8));
         };
         auto MB = [&](int ub, int ks, int p, int first) __attribute__((always_inline)) {
-            if (!CH || (RLT_W6_ABL & 4)) return;
+            if (!CH) return;
             const int bp = p == 2 ? 2 : (p == 0 || p == 4) ? 1 : 0;              // dA plane: m, h, l, h, m, h
             const bf16x8 bv = bfr[ks & 1][bp];
             f32x4& d = acc[X][ub];
@@ -509,7 +480,7 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
         auto TR = [&](int u, int r) __attribute__((always_inline)) { if (EL) tcv[r] = __builtin_amdgcn_rcpf(tcv[r]); };
         auto T5 = [&](int u) __attribute__((always_inline)) { if (EL) tcv = 2.f * tcv - 1.f; };                         // tanh(c_t)
         auto B1 = [&](int u) __attribute__((always_inline)) { if (EL) dhv = in[10 + u] + acc[Y][u]; };
-        auto LDN = [&](int k) __attribute__((always_inline)) { if (EL && !(RLT_W6_ABL & 2)) load_slot(k, SINGLE ? Y : X, rgN, rcpN, rdhN); };
+        auto LDN = [&](int k) __attribute__((always_inline)) { if (EL) load_slot(k, SINGLE ? Y : X, rgN, rcpN, rdhN); };
         auto B2 = [&](int u) __attribute__((always_inline)) { if (EL) t0 = dhv * in[4 * u + 3]; };
         auto B3 = [&](int u) __attribute__((always_inline)) { if (EL) { t1 = tcv * tcv; t1 = 1.f - t1; } };
         auto B5 = [&](int u) __attribute__((always_inline)) { if (EL) { t0 = t0 * t1; dcu = t0 + dc[Y][u]; } };
@@ -531,7 +502,7 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
         auto B17 = [&](int u) __attribute__((always_inline)) { if (EL) dc[Y][u] = dcu * in[4 * u + 1]; };
         auto B18 = [&](int u) __attribute__((always_inline)) { if (EL) in[4 * u + 1] = t0 * t1; };                     // dA_f
         auto ST = [&](int u, int g) __attribute__((always_inline)) {
-            if (EL && !(RLT_W6_ABL & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, in[4 * u + g]), rgY, voff_g[Y] + 512 * g + 64 * u, 0, 0);
+            if (EL) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, in[4 * u + g]), rgY, voff_g[Y] + 512 * g + 64 * u, 0, 0);
         };
         // split of the chunk of units r = 2 ch, 2 ch + 1 (slots i f g o | i f g o), residuals in place
         auto SP = [&](int u, int ch, int part) __attribute__((always_inline)) {
@@ -539,11 +510,11 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
             f32x4 &vi = in[4 * u], &vf = in[4 * u + 1], &vg = in[4 * u + 2], &vo = in[4 * u + 3];
             const int r0 = 2 * ch, r1 = 2 * ch + 1;
             auto hi4 = [&](uint32_t (&o4)[4]) __attribute__((always_inline)) {
-                o4[0] = pk2w(vi[r0], vf[r0]); o4[1] = pk2w(vg[r0], vo[r0]); o4[2] = pk2w(vi[r1], vf[r1]); o4[3] = pk2w(vg[r1], vo[r1]);
+                o4[0] = pk2(vi[r0], vf[r0]); o4[1] = pk2(vg[r0], vo[r0]); o4[2] = pk2(vi[r1], vf[r1]); o4[3] = pk2(vg[r1], vo[r1]);
                 asm("" : "+v"(o4[0]), "+v"(o4[1]), "+v"(o4[2]), "+v"(o4[3]));
             };
             auto res = [&](const uint32_t (&o4)[4], int r, int k) __attribute__((always_inline)) {
-                vi[r] -= bf_lo(o4[k]); vf[r] -= bf_hi(o4[k]); vg[r] -= bf_lo(o4[k + 1]); vo[r] -= bf_hi(o4[k + 1]);
+                vi[r] -= lo16(o4[k]); vf[r] -= hi16(o4[k]); vg[r] -= lo16(o4[k + 1]); vo[r] -= hi16(o4[k + 1]);
             };
             if (part == 0) hi4(h4);
             if (part == 1) res(h4, r0, 0);
@@ -562,7 +533,6 @@ __global__ __launch_bounds__(256, 1) void bilstm6w_bwd_kernel(float* __restrict_
         GAP_END;
 #include "lstm6w_bwd_body.inc"
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        for (int i = 0; i < w * RLT_W6_STAGGER; ++i) asm volatile("s_nop 15");
     };
     const std::integral_constant<int, 0> H0;
     const std::integral_constant<int, 1> H1;

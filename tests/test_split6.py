@@ -1,5 +1,5 @@
-"""The arithmetic claim behind the library's bf16x6 mode (include/rlt_hip.h RLT_PRECISION_BF16X6; csrc/gemm.hip split4x3,
-csrc/attention6.hip split4x3_6), restated in numpy and checked on the CPU:
+"""The arithmetic claim behind the library's bf16x6 mode (include/rlt_hip.h RLT_PRECISION_BF16X6; implemented once, in
+csrc/split6.h: split4x3 / split8x3 and the product order x6_plane_a / x6_plane_b), restated in numpy and checked on the CPU:
 
   * every fp32 value splits EXACTLY into three bf16 values, x = h + m + l with h = bf16(x), m = bf16(x - h),
     l = x - h - m (round-to-nearest-even conversions, the residuals formed in fp32) - over the whole fp32 range except

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel A/B experiments: build librlt_hip.so again with extra -D flags for ONE source file, next to the product build.
 
-    python tools/build_variant.py NAME attention3.hip -DRLT_EXP_PIPE2 [-D...]
+    python tools/build_variant.py NAME attention6.hip -DRLT_PP_STAMPS [-D...]
 
 -> ranked-list-truncation_amd/csrc/variants/librlt_NAME.so (travels to the GPU box; select it with RLT_HIP_LIB=<path>,
 tools/bench_kernels.py prints kernel times).  The product library is untouched."""
