@@ -272,6 +272,34 @@ int rlt_cut_metrics_ex(const float* p, const float* labels, const int32_t* k_in,
 int rlt_task_metrics(const float* labels, const float* pred, int B, int S,
                      double* dcg_out, double* auc_out, double* sums, void* stream);
 
+/* ------------------------------------------------------------------ rerank, then truncate (csrc/rerank.hip)
+ * A stable per-list sort by descending pred (B,S) that carries up to four companion (B,S) fp32 arrays along - the labels, the
+ * retrieval score, the cut distribution, the class probability - so that every evaluation pass above and below runs unchanged
+ * on the re-ranked lists.
+ * The order of list b is exactly that of np.argsort(-pred[b], kind="stable") on float32: values descend; equal values keep
+ * their original order, and +0.0 == -0.0 is a tie; every NaN comes after every number, in original order; +inf is first and
+ * -inf last among the numbers.  This is a TOTAL order - every element is sorted by one 64-bit key, (an integer image of the
+ * value, NaN mapped behind -inf) << 32 | original index, and the keys of a list are distinct - so perm is a permutation and
+ * rank its inverse for ANY input bits.  (The `pi > pj || (pi == pj && i < j)` rank inside rlt_task_metrics is not a
+ * permutation when NaNs are present; on NaN-free input the two orders agree.)
+ * Outputs (each may be NULL, but not all of them with n == 0):
+ *   perm (B,S) int32: perm[b,i] = original index of the document at new position i;
+ *   rank (B,S) int32: rank[b,j] = new position of original document j, the inverse of perm;
+ *   sorted_pred (B,S): sorted_pred[b,i] = pred[b,perm[b,i]], the same bits (NaN payloads and the sign of zero included);
+ *   dst[t] (B,S), t < n: dst[t][b,i] = src[t][b,perm[b,i]], the same bits.
+ * src, dst: HOST arrays of n device pointers, 0 <= n <= 4 (not read for n == 0).  No dst[t] or sorted_pred may overlap pred or
+ * any src[t]: the caller's duty, not checked.
+ * S in 1..1024, any B >= 1 (64-bit element offsets).  A group of 16, 32 or 64 lanes owns a list (S <= 64: four lists per
+ * wavefront, S <= 128: two, else one), four wavefronts per workgroup; the keys stay in registers through a bitonic network
+ * (exchanges inside a lane and between lanes), perm goes through the wavefront's LDS and the companions are gathered through it.
+ * One launch, no workspace, no atomics, no allocation, no host synchronisation: two calls give the same bits.
+ * Errors before any launch, in this order: RLT_E_ARG (pred NULL; non-positive B or S; n outside 0..4; n > 0 with src or dst
+ * NULL, or a NULL entry among their first n; nothing to write), RLT_E_SHAPE (S > 1024), RLT_E_ALIGN (any pointer off 4 bytes:
+ * rows are read and written 4 bytes at a time, no 16-byte requirement).
+ * Algorithmic bytes per list: read 4 S (1 + n), write up to 4 S (3 + n). */
+int rlt_rerank_lists(const float* pred, int B, int S, const float* const* src, float* const* dst, int n,
+                     int32_t* perm, int32_t* rank, float* sorted_pred, void* stream);
+
 /* ------------------------------------------------------------------ truncation baselines
  * The reference's Baseline/ notebooks (Oracle, Fixed-k, Greedy-k, Truncation_analysis) from one pass over labels (B,S),
  * 0/1 in rank order, S in 1..1024.  With c_k = the sum of the first k labels and N = the sum of the list, for k = 1..S:

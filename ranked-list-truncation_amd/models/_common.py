@@ -92,6 +92,24 @@ def pick_tasks(num_tasks):
     return ["rerank", "decison_layer"]
 
 
+class _CallableHead:
+    """The `rerank` parameter holder of a model (every attribute is the holder's), callable as the model's `rerank_order`."""
+    __slots__ = ("_head", "_call")
+
+    def __init__(self, head, call):
+        object.__setattr__(self, "_head", head)
+        object.__setattr__(self, "_call", call)
+
+    def __getattr__(self, name):
+        return getattr(self._head, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._head, name, value)
+
+    def __call__(self, x, by="rerank"):
+        return self._call(x, by=by)
+
+
 class CutModel(nn.Module):
     """Common base of the truncation models: `truncate` says where the model cuts each list, with no labels."""
 
@@ -118,3 +136,49 @@ class CutModel(nn.Module):
         finally:
             self.train(was_training)
         return per["k"], per["p_k"]
+
+    _TOWER_HEADS = {"TowerClass": "classi", "TowerRerank": "rerank", "TowerCut": "decison_layer"}
+
+    def head_names(self):
+        """The names of the model's outputs in the order forward returns them ('classi', 'rerank', 'decison_layer'): the towers
+        of the expert models, the task code of MtAttnCut / MtChoopy; () for a model with the cut head alone."""
+        if hasattr(self, "towers"):
+            return tuple(self._TOWER_HEADS.get(type(t).__name__, "") for t in self.towers)
+        if hasattr(self, "num_tasks"):
+            return tuple(pick_tasks(self.num_tasks))
+        return ()
+
+    def __getattr__(self, name):
+        # `model.rerank(x, by=...)` beside the `rerank` parameter holder of MtAttnCut / MtChoopy, whose state_dict keys are the
+        # reference's: the holder, where there is one, comes back callable
+        if name == "rerank":
+            head = self.__dict__.get("_modules", {}).get("rerank")
+            return self.rerank_order if head is None else _CallableHead(head, self.rerank_order)
+        return super().__getattr__(name)
+
+    def rerank_order(self, x, by="rerank"):
+        """`model.rerank(x, by=...)`.  x: what forward takes.  Runs the model in eval mode under no_grad and returns
+        (perm (B,S) int32, k (B,) int32) on the device: the order of each list by the auxiliary head `by` ('rerank' | 'classi'), descending and stable
+        (ops.rerank_lists: perm[b,i] = the original index of the document at new position i), and the model's own cut as
+        `truncate` gives it.  The module's train / eval state is restored.  A model, or a num_tasks, without that head is a
+        ValueError: the cut head never stands in for it."""
+        if by not in ("rerank", "classi"):
+            raise ValueError(f"rerank: by must be 'rerank' or 'classi', got {by!r}")
+        names = self.head_names()
+        if by not in names:
+            raise ValueError(f"{type(self).__name__}{' with num_tasks=%s' % self.num_tasks if hasattr(self, 'num_tasks') else ''} "
+                             f"has no {by!r} head (its outputs: {list(names) or ['the cut distribution']})")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = self(x)
+                if isinstance(out, tuple) and isinstance(out[-1], (list, tuple)):       # ProbeBase: (h, experts, towers)
+                    out = out[-1]
+                if len(out) != len(names):
+                    raise ValueError(f"{type(self).__name__} returned {len(out)} outputs for the heads {list(names)}")
+                perm = ops.rerank_lists(out[names.index(by)])[0]
+                per, _ = ops.cut_report(out[-1])
+        finally:
+            self.train(was_training)
+        return perm, per["k"]

@@ -58,6 +58,8 @@ _SIGNATURES = {
     "rlt_wass_loss_fwd": (c_int, [P, P, c_int, c_int, c_float, c_int, c_float, P, P, c_size_t, P]),
     "rlt_wass_loss_bwd": (c_int, [P, P, P, c_int, c_int, c_float, c_int, P, c_size_t, P, P]),
     "rlt_task_metrics": (c_int, [P, P, c_int, c_int, P, P, P, P]),
+    # stable per-list sort by a head's values, the companion arrays carried along (csrc/rerank.hip)
+    "rlt_rerank_lists": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P, P]),
     "rlt_truncation_curves_workspace": (c_size_t, [c_int, c_int]),
     "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_cut_report_workspace": (c_size_t, [c_int, c_int]),

@@ -1445,6 +1445,47 @@ def cut_sweep(v, thresholds, rule, labels=None, penalty=-1.0, beta=1.0, curve=No
     return k, curve
 
 
+RERANK_MAX_ARRAYS = 4
+
+
+def rerank_lists(pred, *arrays, want_perm=True, want_rank=False, want_sorted=False):
+    """Stable per-list sort by descending `pred` with up to four companion arrays carried along (rlt_rerank_lists).  pred: (B,S)
+    or (B,S,1) head values; arrays: (B,S) / (B,S,1) tensors - labels, retrieval scores, the cut distribution.  The order of a
+    list is np.argsort(-pred[b], kind="stable"): NaNs last, +0 and -0 tied.  Returns (perm, rank, sorted_pred, [permuted arrays]):
+    perm (B,S) int32 = original index at each new position, rank its inverse, sorted_pred = pred in the new order, each None
+    unless asked for; the permuted arrays are fresh (B,S) fp32 tensors with the same bits.  Tensors in and out, no host read.
+    Not a tape node: an input that requires grad under grad mode raises."""
+    if len(arrays) > RERANK_MAX_ARRAYS:
+        raise ValueError(f"rerank_lists: {len(arrays)} companion arrays, at most {RERANK_MAX_ARRAYS}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (pred,) + arrays):
+        raise RuntimeError("rerank_lists is not differentiable: detach the inputs or call it under torch.no_grad()")
+    N.require_cuda(pred, *arrays)
+
+    def rows(t, what):
+        t = N.f32c(t.detach())
+        if t.dim() == 3 and t.shape[2] == 1:
+            t = t.reshape(t.shape[0], t.shape[1])
+        if t.dim() != 2:
+            raise ValueError(f"rerank_lists: {what} must be (B,S) or (B,S,1); got {tuple(t.shape)}")
+        return t
+    pred = rows(pred, "pred")
+    B, S = pred.shape
+    dev = pred.device
+    src = [rows(t, "a companion array") for t in arrays]
+    for t in src:
+        if tuple(t.shape) != (B, S):
+            raise ValueError(f"rerank_lists: a companion array {tuple(t.shape)} does not match pred's {(B, S)}")
+    if not (src or want_perm or want_rank or want_sorted):
+        raise ValueError("rerank_lists: nothing asked for")
+    dst = [torch.empty_like(t) for t in src]
+    perm = torch.empty((B, S), dtype=torch.int32, device=dev) if want_perm else None
+    rank = torch.empty((B, S), dtype=torch.int32, device=dev) if want_rank else None
+    sorted_pred = _empty((B, S), pred) if want_sorted else None
+    call("rlt_rerank_lists", ptr(pred), B, S, N.pointer_array(src) if src else None, N.pointer_array(dst) if dst else None,
+         len(src), ptr(perm), ptr(rank), ptr(sorted_pred), stream())
+    return perm, rank, sorted_pred, dst
+
+
 def neighbor_features(doc_ids, table, out=None, col=0, validate=True):
     """AttnCut's neighbour-similarity statistics (rlt_neighbor_features): doc_ids (B,S) int32 rows of `table` in rank order ->
     per position the cosine similarity to the neighbouring documents, the tf-idf column first, then the doc2vec one.

@@ -90,6 +90,7 @@ class ScalarLog:
 
 class Trainer:
     attention_axis = "list"      # of a trainer a driver assembles by hand (verify_probe.py); __init__ sets the run's
+    rerank_by = None             # --rerank-eval, likewise
 
     def __init__(self, args):
         self.args = args
@@ -184,6 +185,9 @@ class Trainer:
             raise ValueError(f"model {name!r} is outside the HIP hot path "
                              "(bicut, choopy, attncut, mtchoopy, mtattncut, mmoecut, moecut, mtple)")
         self.multi_task = name in ('mtchoopy', 'mtattncut', 'mmoecut', 'moecut', 'mtple')   # reference: `'m' in model_name`
+        self.rerank_by = getattr(args, "rerank_eval", None)     # (drivers build their own Namespace)
+        if self.rerank_by and self.rerank_by not in getattr(self.model, "head_names", tuple)():
+            raise ValueError(f"--rerank-eval {self.rerank_by}: {name} with --num-tasks {args.num_tasks} has no such head")
         self.model = self.model.to(self.device)
         if args.ft and self.model_path and os.path.exists(self.model_path):
             self.load_model()
@@ -325,7 +329,48 @@ class Trainer:
                 self.save_model()
         if dcg > self.best_test_dcg:
             self.best_test_dcg = dcg
+        if self.rerank_by and self.rank == 0:
+            self._test_reranked(epoch)
         return loss, f1, dcg
+
+    def _forward_heads(self, x):
+        """(the values of the --rerank-eval head, the cut distribution) of one batch, eval mode, no gradient."""
+        self.model.eval()
+        with torch.no_grad():
+            out = self.model(x.to(self.device, non_blocking=True))
+        return out[self.model.head_names().index(self.rerank_by)], out[-1]
+
+    def _reranked_eval(self, L):
+        from utils.rerank import RerankedEval
+        ks = [int(k) for k in str(self.args.fixed_k).split(',') if k.strip()]
+        return RerankedEval(L, by=self.rerank_by, metric=report_metric(self.args.criterion), reward=eval_reward_spec(self.args),
+                            fixed_k=ks, device=self.device)
+
+    def _test_reranked(self, epoch):
+        """--rerank-eval: the test lists once more through the model, every figure in the retrieval order and in the head's
+        order (utils/rerank.py).  No collective: rank 0 calls it."""
+        from utils.rerank import mean_over_lengths
+        evals = {}
+        for X, y in self.test_loader:
+            L = int(X.shape[1])
+            if L not in evals:
+                evals[L] = self._reranked_eval(L)
+            head, cut = self._forward_heads(X)
+            evals[L].update(head, cut, y)
+        summ = {str(L): ev.summary() for L, ev in sorted(evals.items())}
+        means = mean_over_lengths(summ)
+        for m, tag in (("f1", "F1"), ("dcg", "DCG")):
+            self.writer.add_scalar('test/{}_orig_epoch'.format(tag), means["orig"][m], epoch)
+            self.writer.add_scalar('test/{}_rr_epoch'.format(tag), means["rr"][m], epoch)
+        for L, s in summ.items():
+            for name, v in s["rr"].items():
+                self.writer.add_scalar('test_rr/{}'.format(name), v, epoch * 100000 + int(L))
+        logging.info('\tTest, re-ranked by {}: f1 = {:.6f} -> {:.6f} | dcg = {:.6f} -> {:.6f}\n'.format(
+            self.rerank_by, means["orig"]["f1"], means["rr"]["f1"], means["orig"]["dcg"], means["rr"]["dcg"]))
+        if self.history and self.history[-1]["epoch"] == epoch:
+            self.history[-1]["test_rr"] = {"by": self.rerank_by, "f1": means["orig"]["f1"], "f1_rr": means["rr"]["f1"],
+                                           "dcg": means["orig"]["dcg"], "dcg_rr": means["rr"]["dcg"], "lengths": summ}
+        return summ
 
     def _warn_axis(self, stored, path):
         if stored != self.attention_axis:
@@ -460,11 +505,20 @@ class Trainer:
         spec = eval_reward_spec(self.args) if labelled else None
         for L, qids, x, y in self._split_batches(split):
             rep = CutReport(L, metric=report_metric(self.args.criterion), device=self.device, reward=spec)
+            rr = self._reranked_eval(L) if self.rerank_by and labelled else None
             for i in range(0, x.shape[0], self.batch_size):
-                cut = self._forward_eval(x[i:i + self.batch_size])
+                if rr is not None:              # one forward pass serves both
+                    head, cut = self._forward_heads(x[i:i + self.batch_size])
+                    rr.update(head, cut, y[i:i + self.batch_size])
+                else:
+                    cut = self._forward_eval(x[i:i + self.batch_size])
                 rep.update(cut, y[i:i + self.batch_size] if labelled else None)
             for name, a in rep.per_query().items():
                 arrays.setdefault(name, []).append(a)
+            if rr is not None:
+                for name, a in rr.per_query().items():
+                    if name.endswith("_rr"):
+                        arrays.setdefault(name, []).append(a)
             qid_all += [str(q) for q in qids]
             len_all += [L] * len(qids)
             reward, pred = rep.curves(tail_fix=True)
@@ -481,6 +535,8 @@ class Trainer:
         if spec is not None:                    # the reward the reward columns are in: compare_reports(metric='reward') checks it
             per_len["reward_spec"] = np.asarray(eval_reward_text(spec))
         per_len["attention_axis"] = np.asarray(self.attention_axis)
+        if self.rerank_by and labelled:
+            per_len["rerank_by"] = np.asarray(self.rerank_by)
         np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
                  summary=np.asarray(json.dumps(summaries)), **{k: np.concatenate(v) for k, v in arrays.items()}, **per_len)
         return summaries
@@ -740,6 +796,10 @@ def build_parser():
                         "X, the retrieval score, falls below tau; no model; score:auto:N takes N quantiles of the train scores); "
                         "logs the test curve and the test figures at the train-tuned tau* beside the argmax cut's")
     p.add_argument('--sweep-out', type=str, default=None, help="--cut-sweep writes its curves and the tuned figures here (.npz or .json)")
+    p.add_argument('--rerank-eval', type=str, default=None, choices=('rerank', 'classi'),
+                   help="a multi-task model's auxiliary head: every test pass also re-ranks each test list by that head's values "
+                        "(stable, descending) and logs F1 / DCG at the model's k and the best-cut figures in both orders (test/..._rr "
+                        "scalars, `test_rr` in --history-json); --report-out gains *_rr per-query arrays and rerank_by")
     p.add_argument('--draw', type=int, default=0, choices=(0, 1),
                    help="1: on even epochs, the reward and prediction curves of the reference's figure for every test batch of more "
                         "than 40 lists go to scalars.jsonl (draw/reward, draw/prediction); no image is written")

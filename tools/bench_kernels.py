@@ -1309,6 +1309,79 @@ def seq_attention(shapes=((4096, 300, 4, 64), (8192, 300, 8, 16)), reps=7, runs=
             torch.cuda.empty_cache()
 
 
+def rerank(shapes=((4096, 300), (1048576, 300)), companions=(1, 3), reps=7, runs=2):
+    """rlt_rerank_lists (perm, rank, sorted values and n companion arrays: every output on) against the torch compositions a user
+    would otherwise write: torch.sort(-pred, stable=True) + a gather per array (+ a scatter for rank), and argsort +
+    take_along_dim.  The median of `reps` HIP-event timings in each of `runs` separate runs; GB/s on the pass's algorithmic bytes,
+    4 S (1 + n) read + 4 S (3 + n) written per list, against the 8 TB/s of HBM.  (torch's descending order differs on NaNs; the
+    inputs here hold none.)"""
+    import statistics
+    HBM = 8000.0
+
+    def median_ms(fn):
+        fn()                                                     # warm-up: code objects, allocator
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return statistics.median(ts)
+
+    for B, S in shapes:
+        g = torch.Generator(device=dev).manual_seed(5)
+        pred = torch.randn(B, S, device=dev, generator=g)
+        pred[:, ::7] = torch.round(pred[:, ::7])                 # some ties: the order must be the stable one
+        for n in companions:
+            arrays = [torch.rand(B, S, device=dev, generator=g) for _ in range(n)]
+            res = {}
+
+            def fused():
+                res["fused"] = ops.rerank_lists(pred, *arrays, want_perm=True, want_rank=True, want_sorted=True)
+
+            def sort_gather():
+                neg, idx = torch.sort(-pred, dim=1, stable=True)
+                rank = torch.empty_like(idx).scatter_(1, idx, torch.arange(S, device=dev).expand(B, S))
+                res["sort"] = (idx, rank, -neg, [a.gather(1, idx) for a in arrays])
+
+            def argsort_take():
+                idx = torch.argsort(pred, dim=1, descending=True, stable=True)
+                rank = torch.argsort(idx, dim=1)
+                res["argsort"] = (idx, rank, torch.take_along_dim(pred, idx, 1), [torch.take_along_dim(a, idx, 1) for a in arrays])
+            fns = (("rlt_rerank_lists, every output", fused), ("torch.sort(stable) + gather + scatter", sort_gather),
+                   ("torch.argsort x2 + take_along_dim", argsort_take))
+            for _name, fn in fns:
+                fn()
+            torch.cuda.synchronize()
+            perm, rank, srt, moved = res["fused"]
+            for key in ("sort", "argsort"):
+                idx, rk, sv, mv = res[key]
+                assert torch.equal(perm.long(), idx) and torch.equal(rank.long(), rk) and torch.equal(srt, sv)
+                assert all(torch.equal(a, b) for a, b in zip(moved, mv))
+            res.clear()
+            del perm, rank, srt, moved, idx, rk, sv, mv
+            torch.cuda.empty_cache()
+            nbytes = (4.0 * S * (1 + n) + 4.0 * S * (3 + n)) * B
+            for r in range(runs):
+                med = {}
+                for name, fn in fns:
+                    med[name] = median_ms(fn)
+                    res.clear()
+                    torch.cuda.empty_cache()
+                for name, _fn in fns:
+                    gbs = nbytes / med[name] / 1e6
+                    print(f"rerank B{B} S{S} n{n} run {r} {name:40s}: {med[name] * 1e3:10.1f} us  {gbs:8.1f} GB/s on the algorithmic "
+                          f"bytes ({100 * gbs / HBM:4.1f} % of 8 TB/s)", flush=True)
+                best = min(med[name] for name, _fn in fns[1:])
+                print(f"rerank B{B} S{S} n{n} run {r} best torch composition / rlt_rerank_lists: {best / med[fns[0][0]]:.2f}x"
+                      + ("  (SLOWER than the torch composition here)" if med[fns[0][0]] > best else ""), flush=True)
+            del arrays
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
