@@ -300,6 +300,57 @@ int rlt_task_metrics(const float* labels, const float* pred, int B, int S,
 int rlt_rerank_lists(const float* pred, int B, int S, const float* const* src, float* const* dst, int n,
                      int32_t* perm, int32_t* rank, float* sorted_pred, void* stream);
 
+/* ------------------------------------------------------------------ pairwise ranking losses (csrc/pair_rank.hip)
+ * RankNet and LambdaRank on the scores of a rerank head: a pairwise logistic loss over the documents of each list, its gradient,
+ * and - as a by-product of the same O(S^2) pass - the counting rank of every document.  score, labels: (B,S) fp32.
+ * Definitions for list b:
+ *   grade g_i: the rule of rlt_reward_spec - the label rounded to the nearest integer and clamped to 0..n_grades-1; NaN gives 0.
+ *     n_grades in 2..8.  G_i = gain[g_i]; gain is a HOST array of n_grades floats, NULL = 2^g - 1.
+ *   counting rank pi_i = #{ j : s_j > s_i, or s_j == s_i and j < i }, 0-based (+0 == -0 is a tie).  On NaN-free scores this is
+ *     the inverse permutation rlt_rerank_lists writes as `rank`.  (A NaN compares false with everything: with NaNs present the
+ *     counting rank is not a permutation, see below.)
+ *   D(r) = 1 / log2(r + 2) from dcg_table, the float64 table of rlt_dcg_table_init (8-byte aligned; read by RLT_PAIR_LAMBDARANK
+ *     only).  ideal: the list's ideal value as rlt_reward_spec defines it for a GAIN spec with the table's discount.
+ *   pairs: all (i, j) with g_i > g_j; n_pairs[b] is their count.
+ *   weight: RLT_PAIR_RANKNET w_ij = 1; RLT_PAIR_LAMBDARANK w_ij = |G_i - G_j| * |D(pi_i) - D(pi_j)|, divided by ideal when
+ *     `normalize` is set and ideal > 0.
+ *   x = sigma (s_i - s_j); l_ij = w_ij softplus(-x), softplus(-x) = max(-x, 0) + log1p(exp(-|x|)); lam_ij = -sigma w_ij sigmoid(-x).
+ *   loss_per_list[b]: RANKNET sum l_ij / n_pairs, LAMBDARANK sum l_ij; 0, with a zero gradient, when n_pairs == 0.
+ *   loss_out = (sum over lists) / B from a float64 sum in a fixed order.
+ *   dscore[b,i] = gscale / B * (1 / n_pairs for RANKNET) * (sum_{j: g_i > g_j} lam_ij - sum_{j: g_j > g_i} lam_ji): the LambdaRank
+ *     gradient (the weights are constants); for RANKNET the true gradient of loss_out.  gscale: device scalar, NULL = 1; it
+ *     scales dscore and nothing else.
+ *   A list with a NaN score has NaN loss_per_list and a NaN row of dscore, and makes loss_out NaN; its n_pairs is still exact
+ *     and its rank_out follows the definition above.  Every other list's outputs are the bits they would be without it.
+ * Outputs, each may be NULL but not all of them: loss_per_list (B) fp32, loss_out (1) fp32, dscore (B,S) fp32, rank_out (B,S)
+ * int32, n_pairs (B) int32.
+ * Arithmetic: s_i - s_j, x, the weight and every sum over j are float64 (the discount differences cancel); exp, log1p and the
+ * sigmoid's division are fp32 on the fp32 head of |x|, its float64 tail applied as a first-order factor, so exp(-|x|) keeps its
+ * relative accuracy on the saturated branch.  Pairs with g_i == g_j cost no transcendental.
+ * Layout: S in 1..1024 (RLT_E_SHAPE beyond), any B >= 1 (64-bit element offsets).  A group of lanes inside one wavefront owns a
+ * list: 16 lanes for S <= 64 (four lists per wavefront), 32 for S <= 128 (two), the whole wavefront beyond; a lane owns the
+ * documents hl, hl + L, ... (4 of them up to S = 256, 8 up to 512, 16 up to 1024).  A workgroup has 4 wavefronts (2 for S > 512):
+ * 16, 8, 4, 4 or 2 lists per workgroup.  The list's scores, grades and D(pi) live in the wavefront's LDS and are read as
+ * broadcasts; a lane walks all j for its own documents and forms its own dscore from both sides of each of its pairs: no sum
+ * crosses lanes for dscore, no atomics.  The grid is sized to the chip and strides over the lists.  One launch for the pass (every
+ * workgroup leaves one float64 record in ws), then - only when loss_out is given - a one-workgroup fixed-order reduction.  No
+ * allocation, no host synchronisation, capturable into a graph: two calls give the same bits.
+ * ws: rlt_pair_rank_workspace(B, S) bytes, 8-byte aligned (0 for B <= 0 or S outside 1..1024; never smaller for a larger B).
+ * Errors before any launch, in this order: RLT_E_ARG (score, labels or ws NULL; non-positive B or S; kind outside its codes;
+ * sigma not finite or <= 0; n_grades outside 2..8; a non-finite gain; RLT_PAIR_LAMBDARANK with dcg_table NULL; every output NULL),
+ * RLT_E_SHAPE (S > 1024), RLT_E_ALIGN (ws or dcg_table off 8 bytes; any other device pointer off 4: rows are read and written 4
+ * bytes at a time, no 16-byte requirement), RLT_E_WORKSPACE.
+ * Algorithmic bytes per list: read 8 S, write up to 8 S + 8; S^2 pair visits, of which the pairs of unequal grade (twice
+ * n_pairs: each is seen from both sides) pay one exp and a division, half of them also one log1p. */
+#define RLT_PAIR_RANKNET    0
+#define RLT_PAIR_LAMBDARANK 1
+size_t rlt_pair_rank_workspace(int B, int S);
+int rlt_pair_rank_loss(const float* score, const float* labels, int B, int S, int kind, float sigma,
+                       const float* gain, int n_grades, int normalize,
+                       const void* dcg_table, const float* gscale,
+                       float* loss_per_list, float* loss_out, float* dscore,
+                       int32_t* rank_out, int32_t* n_pairs, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ truncation baselines
  * The reference's Baseline/ notebooks (Oracle, Fixed-k, Greedy-k, Truncation_analysis) from one pass over labels (B,S),
  * 0/1 in rank order, S in 1..1024.  With c_k = the sum of the first k labels and N = the sum of the list, for k = 1..S:

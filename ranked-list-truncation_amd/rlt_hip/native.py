@@ -23,6 +23,8 @@ CUT_ARGMAX, CUT_PAIR = 0, 1
 SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE = 0, 1, 2
 SWEEP_COLS, SWEEP_MAX_T = 8, 64
 REWARD_FBETA, REWARD_GAIN, REWARD_MAX_GRADES = 0, 1, 8
+PAIR_RANKNET, PAIR_LAMBDARANK = 0, 1
+PAIR_KINDS = {"ranknet": PAIR_RANKNET, "lambdarank": PAIR_LAMBDARANK}
 SWEEP_ROWS = ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut", "n_lists")      # the rows of rlt_cut_sweep's curve
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
@@ -60,6 +62,9 @@ _SIGNATURES = {
     "rlt_task_metrics": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     # stable per-list sort by a head's values, the companion arrays carried along (csrc/rerank.hip)
     "rlt_rerank_lists": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P, P]),
+    # RankNet / LambdaRank on a rerank head's scores, with the counting rank (csrc/pair_rank.hip)
+    "rlt_pair_rank_workspace": (c_size_t, [c_int, c_int]),
+    "rlt_pair_rank_loss": (c_int, [P, P, c_int, c_int, c_int, c_float, P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_truncation_curves_workspace": (c_size_t, [c_int, c_int]),
     "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
     "rlt_cut_report_workspace": (c_size_t, [c_int, c_int]),

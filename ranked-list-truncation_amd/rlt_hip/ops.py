@@ -1246,6 +1246,85 @@ class RerankLossFn(Function):
         return d.view(ctx.sshape), None, None
 
 
+def _pair_rank_args(kind, sigma, gains, n_grades):
+    """(kind code, gain array or None, n_grades) of a rlt_pair_rank_loss call; gains=None is the library's 2^g - 1."""
+    if isinstance(kind, str):
+        if kind not in N.PAIR_KINDS:
+            raise ValueError(f"pair rank kind must be one of {sorted(N.PAIR_KINDS)}, got {kind!r}")
+        kind = N.PAIR_KINDS[kind]
+    if not (float(sigma) > 0 and math.isfinite(float(sigma))):
+        raise ValueError(f"sigma must be positive and finite, got {sigma!r}")
+    garr = None
+    if gains is not None:
+        gains = [float(g) for g in gains]
+        n_grades = len(gains)
+        garr = (N.c_float * n_grades)(*gains)
+    if not 2 <= int(n_grades) <= N.REWARD_MAX_GRADES:
+        raise ValueError(f"n_grades must be in 2..{N.REWARD_MAX_GRADES}, got {n_grades}")
+    return kind, garr, int(n_grades)
+
+
+def _pair_rows(t, what):
+    t = N.f32c(t)
+    if t.dim() == 3 and t.shape[2] == 1:
+        t = t.reshape(t.shape[0], t.shape[1])
+    if t.dim() != 2:
+        raise ValueError(f"pair_rank: {what} must be (B,S) or (B,S,1); got {tuple(t.shape)}")
+    return t
+
+
+class PairRankLossFn(Function):
+    """RankNet / LambdaRank loss of a rerank head's scores (rlt_pair_rank_loss): the forward makes ONE call that writes the batch
+    loss and d(loss)/d(score); backward only scales that by the incoming gradient.  score, labels: (B,S) fp32."""
+
+    @staticmethod
+    def forward(ctx, score, labels, kind, sigma, gains, n_grades, normalize):
+        kind, garr, n_grades = _pair_rank_args(kind, sigma, gains, n_grades)
+        s = _pair_rows(score, "score")
+        B, S = s.shape
+        dev = s.device
+        loss = _empty((1,), s)
+        ds = _empty((B, S), s)
+        table = dcg_table(dev) if kind == N.PAIR_LAMBDARANK else None
+        ws_bytes = query("rlt_pair_rank_workspace", B, S)
+        ws = workspace(ws_bytes, dev)
+        call("rlt_pair_rank_loss", ptr(s), ptr(labels), B, S, kind, float(sigma), garr, n_grades, int(bool(normalize)),
+             ptr(table), None, None, ptr(loss), ptr(ds), None, None, ptr(ws), ws_bytes, stream())
+        ctx.save_for_backward(ds)
+        ctx.sshape = score.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        (ds,) = ctx.saved_tensors
+        g = ds.clone()
+        go = N.f32c(go).reshape(1)
+        call("rlt_scale", ptr(g), ptr(go), g.numel(), stream())
+        return g.view(ctx.sshape), None, None, None, None, None, None
+
+
+def pair_rank(score, labels, kind="lambdarank", sigma=1.0, gains=None, n_grades=2, normalize=True):
+    """The non-tape form of rlt_pair_rank_loss: (rank (B,S) int32, n_pairs (B) int32, loss_per_list (B) fp32) - the counting
+    rank of every document (on NaN-free scores the `rank` of rerank_lists), the number of pairs of unequal grade per list and
+    the RankNet / LambdaRank loss of each list.  Tensors in and out, no host read."""
+    N.require_cuda(score, labels)
+    kind, garr, n_grades = _pair_rank_args(kind, sigma, gains, n_grades)
+    s = _pair_rows(score.detach(), "score")
+    y = _pair_rows(labels.detach(), "labels")
+    if y.shape != s.shape:
+        raise ValueError(f"pair_rank: labels {tuple(y.shape)} do not match score's {tuple(s.shape)}")
+    B, S = s.shape
+    dev = s.device
+    rank = torch.empty((B, S), dtype=torch.int32, device=dev)
+    n_pairs = torch.empty((B,), dtype=torch.int32, device=dev)
+    per_list = _empty((B,), s)
+    table = dcg_table(dev) if kind == N.PAIR_LAMBDARANK else None
+    ws_bytes = query("rlt_pair_rank_workspace", B, S)
+    ws = workspace(ws_bytes, dev)
+    call("rlt_pair_rank_loss", ptr(s), ptr(y), B, S, kind, float(sigma), garr, n_grades, int(bool(normalize)),
+         ptr(table), None, ptr(per_list), None, None, ptr(rank), ptr(n_pairs), ptr(ws), ws_bytes, stream())
+    return rank, n_pairs, per_list
+
 
 class ProbeHeadsFn(Function):
     """Probe heads on frozen features (rlt_probe_heads): x (S*B,E) -> per-head losses (n,) and activations (n,B,S), with

@@ -26,6 +26,9 @@ state_dict checkpoint on best test F1, run.py:153-232) and the same log lines.  
   * --cut-sweep RULE:LO:HI:N [--sweep-out PATH]: rank 0 evaluates N thresholds of a cut rule (the predicted-mass quantile, the
     first output above tau, or the retrieval score falling below tau) on the train and test lists in one fused pass per batch,
     tunes tau* on train and reports test there beside the argmax cut (utils/sweep.py);
+  * --rerank-loss ranknet|lambdarank [--rerank-sigma F]: the rerank head of a multi-task model is trained with a pairwise logistic
+    loss over the documents of each list (utils.losses.PairwiseRankLoss, one O(S^2) kernel pass) in place of the reference's
+    batch-wide hinge.  Towers that end in a softmax over positions (MMOE, PLE) have score gaps near 1/S and want a large sigma;
   * not carried over: rendering figures and the hyper-parameter random search.
 """
 import argparse
@@ -152,6 +155,13 @@ class Trainer:
         # --attention-axis: 'list' (the reference: lists attend to each other) or 'position' (every list over its own positions);
         # the weights do not depend on it, so it is recorded beside them and a mismatch on loading is a warning, not an error
         self.attention_axis = axis = getattr(args, "attention_axis", "list")
+        # --rerank-loss: the loss of the rerank head inside MtCutLoss - the reference's batch-wide hinge, or a pairwise RankNet /
+        # LambdaRank loss (utils.losses.PairwiseRankLoss); the default builds the criterion exactly as before
+        rr_loss = getattr(args, "rerank_loss", "hinge")
+        rr_kw = {} if rr_loss == "hinge" else {"rerank_loss": rr_loss, "rerank_sigma": getattr(args, "rerank_sigma", 1.0)}
+        if rr_kw and (name not in ('mtchoopy', 'mtattncut', 'mmoecut', 'moecut', 'mtple') or args.num_tasks == 2.1):
+            raise ValueError(f"--rerank-loss {rr_loss}: {name} with --num-tasks {args.num_tasks} has no rerank head to train "
+                             "(the multi-task models with --num-tasks 3 or 2.2 have one)")
         if name == 'bicut':                                                    # run.py:59-64
             self.model = BiCut(input_size=feat, dropout=args.dropout, sparse_input=self.sparse_bicut)
             self.criterion = losses.BiCutLoss(metric=args.criterion)
@@ -165,22 +175,22 @@ class Trainer:
         elif name == 'mtchoopy':                                               # run.py:76-79
             self.model = MtChoopy(seq_len=self.seq_len, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
-                                              classi_weight=args.class_weight, num_tasks=args.num_tasks)
+                                              classi_weight=args.class_weight, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mtattncut':                                              # run.py:80-84
             self.model = MtAttnCut(input_size=feat, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
-                                              classi_weight=args.class_weight, num_tasks=args.num_tasks)
+                                              classi_weight=args.class_weight, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mmoecut':                                                # run.py:85-90 (num_experts exposed)
             self.model = MMOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat,
                                  dropout=args.dropout, num_experts=args.num_experts, attention_axis=axis)
-            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
+            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'moecut':                                                 # run.py:91-96
             self.model = MOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat, dropout=args.dropout,
                                 attention_axis=axis)
-            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
+            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mtple':                                                  # run.py:97-102
             self.model = PLECut(seq_len=self.seq_len, input_size=feat, dropout=args.dropout, num_experts=3, attention_axis=axis)
-            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks)
+            self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         else:
             raise ValueError(f"model {name!r} is outside the HIP hot path "
                              "(bicut, choopy, attncut, mtchoopy, mtattncut, mmoecut, moecut, mtple)")
@@ -796,6 +806,14 @@ def build_parser():
                         "X, the retrieval score, falls below tau; no model; score:auto:N takes N quantiles of the train scores); "
                         "logs the test curve and the test figures at the train-tuned tau* beside the argmax cut's")
     p.add_argument('--sweep-out', type=str, default=None, help="--cut-sweep writes its curves and the tuned figures here (.npz or .json)")
+    p.add_argument('--rerank-loss', type=str, default='hinge', choices=('hinge', 'ranknet', 'lambdarank'),
+                   help="loss of the rerank head in the multi-task criterion: 'hinge' (the reference's batch-wide hinge between "
+                        "the mean irrelevant and the mean relevant score; the default, nothing changes), 'ranknet' (mean pairwise "
+                        "logistic loss per list) or 'lambdarank' (pairs weighted by their nDCG swap gain); weighted by "
+                        "--rerank-weight.  A model without a rerank head rejects a non-default value")
+    p.add_argument('--rerank-sigma', type=float, default=1.0,
+                   help="slope of the pairwise logistic loss, x = sigma (s_i - s_j).  Towers that end in a softmax over positions "
+                        "(MMOE, PLE) have score gaps near 1/S and want a large sigma (of the order of S)")
     p.add_argument('--rerank-eval', type=str, default=None, choices=('rerank', 'classi'),
                    help="a multi-task model's auxiliary head: every test pass also re-ranks each test list by that head's values "
                         "(stable, descending) and logs F1 / DCG at the model's k and the best-cut figures in both orders (test/..._rr "

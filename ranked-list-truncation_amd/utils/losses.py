@@ -1,7 +1,8 @@
 """Reward losses on the HIP hot path - drop-in for the criteria of the reference's utils/losses.py
 that are on the hot path: ChoopyLoss :48-68, AttnCutLoss :71-96, RerankLoss :99-141,
 MtCutLoss :164-191, DivLoss :194-233, BiCutLoss :11-45 and WassDistLoss :236-311 (section 8f row N4).  Same constructor signatures; `criterion(output, labels)`
-returns a 0-d tensor supporting .backward() and .item().
+returns a 0-d tensor supporting .backward() and .item().  PairwiseRankLoss (RankNet / LambdaRank on the rerank head) has no
+counterpart there; MtCutLoss takes it in place of the hinge with `rerank_loss=`.
 
 The reference builds its (B,S) reward matrix with B*S python calls of O(S) tensor ops; here the
 reward matrix, its softmax, the divergence and d(loss)/d(output) come out of ONE kernel pass
@@ -113,11 +114,43 @@ class RerankLoss(nn.Module):
         return ops.RerankLossFn.apply(s, y, float(self.margin))
 
 
+RERANK_LOSSES = ('hinge', 'ranknet', 'lambdarank')
+
+
+class PairwiseRankLoss(nn.Module):
+    """Pairwise logistic ranking loss over the documents of each list (rlt_pair_rank_loss): 'ranknet' - the mean of
+    softplus(-sigma (s_i - s_j)) over the pairs with grade_i > grade_j - or 'lambdarank' - their sum, each pair weighted by
+    |gain_i - gain_j| |D(rank_i) - D(rank_j)| (divided by the list's ideal DCG with `normalize`), the weights held constant in
+    the gradient.  The batch loss is the mean over lists; a list without such a pair gives 0.  gains: gain per grade (its length
+    is n_grades), None = 2^g - 1 over `n_grades` grades; labels are rounded to grades as utils.rewards.RewardSpec does.
+    forward(output, labels): output (B,S,1) or (B,S) scores, labels (B,S)."""
+
+    def __init__(self, kind: str = 'lambdarank', sigma: float = 1.0, gains=None, n_grades: int = 2, normalize: bool = True):
+        super().__init__()
+        ops._pair_rank_args(kind, sigma, gains, n_grades)           # raises on anything the library would refuse
+        self.kind, self.sigma, self.normalize = kind, float(sigma), bool(normalize)
+        self.gains = None if gains is None else tuple(float(g) for g in gains)
+        self.n_grades = int(n_grades) if gains is None else len(self.gains)
+
+    def forward(self, output, labels):
+        N.require_cuda(output, labels)
+        if not (output.dim() == 2 or (output.dim() == 3 and output.shape[2] == 1)):
+            raise ValueError(f"expected (B,S,1) or (B,S) scores, got {tuple(output.shape)}")
+        return ops.PairRankLossFn.apply(N.f32c(output), N.f32c(labels), self.kind, self.sigma, self.gains, self.n_grades,
+                                        self.normalize)
+
+
 class MtCutLoss(nn.Module):
     def __init__(self, metric: str = 'f1', rerank_weight: float = 0.5, classi_weight: float = 0.5,
-                 num_tasks: float = 3):
+                 num_tasks: float = 3, rerank_loss: str = 'hinge', rerank_sigma: float = 1.0):
         super().__init__()
+        if rerank_loss not in RERANK_LOSSES:
+            raise ValueError(f"rerank_loss must be one of {RERANK_LOSSES}, got {rerank_loss!r}")
         self.rerank_weight, self.classi_weight = rerank_weight, classi_weight
+        # 'hinge': the reference's batch-wide RerankLoss, on exactly the path it always took; 'ranknet' / 'lambdarank': a
+        # PairwiseRankLoss on the rerank head in its place (binary relevance, label >= 0.5, as the hinge and the BCE see it)
+        self.rerank_loss = rerank_loss
+        self.pairloss = None if rerank_loss == 'hinge' else PairwiseRankLoss(kind=rerank_loss, sigma=rerank_sigma)
         # the reference registers this (unused) parameter too (utils/losses.py:173): kept for
         # state_dict / RNG-consumption compatibility
         self.weights = nn.Parameter(torch.randn(int(num_tasks)), requires_grad=True)
@@ -137,6 +170,15 @@ class MtCutLoss(nn.Module):
         p, y = _prep(y_cut, labels)
         rr = None if y_rerank is None else N.f32c(y_rerank)
         cl = None if y_class is None else N.f32c(y_class)
+        if self.pairloss is not None and rr is not None:
+            # cut term + w_r * pair loss + w_c * BCE, added on the tape in that order; the BCE from the multi-task pass
+            # without a rerank input, the cut term on whichever pass the metric selects
+            cut = _reward_loss(p, y, self.metric, N.LOSS_JS, float(self.cutloss.tau), with_metrics, self)
+            total = (cut[0] if with_metrics else cut) + float(self.rerank_weight) * self.pairloss(rr, y)
+            if cl is not None:
+                total = total + ops.MtSideLossFn.apply(None, cl, y, float(self.rerank_weight), float(self.classi_weight),
+                                                       float(self.rerankloss.margin))
+            return (total,) + tuple(cut[1:]) if with_metrics else total
         if _spec(self.metric) is not None:
             # any other reward: the cut term on rlt_reward_any_loss, the rerank hinge and the BCE from the multi-task pass with a
             # zero cut term of its own, added on the tape in the reference's order (cut + w_r * hinge + w_c * bce)

@@ -1382,6 +1382,84 @@ def rerank(shapes=((4096, 300), (1048576, 300)), companions=(1, 3), reps=7, runs
             torch.cuda.empty_cache()
 
 
+def pair_rank(shapes=((4096, 300), (1048576, 40)), reps=7, runs=2):
+    """rlt_pair_rank_loss (loss + dscore in one call, ops.PairRankLossFn's forward) against a tiled torch composition of the same
+    loss (s[:, :, None] - s[:, None, :], softplus, masks, autograd; tiles of lists so that the (b,S,S) temporaries stay near
+    0.5 GB) and against the hinge it replaces (rlt_mt_terms + rlt_mt_terms_bwd).  0/1 labels at about 5 % relevant and 4 grades;
+    RankNet and LambdaRank.  The median of `reps` HIP-event timings in each of `runs` separate runs; pair visits per second on
+    the S^2 ordered pairs of every list."""
+    import statistics
+    from rlt_hip import native as N
+
+    def median_ms(fn):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return statistics.median(ts)
+
+    ops.dcg_table(dev)
+    for B, S in shapes:
+        g = torch.Generator(device=dev).manual_seed(5)
+        score = torch.randn(B, S, device=dev, generator=g)
+        tile = max(1, min(B, (1 << 27) // (S * S)))
+        disc = 1.0 / torch.log2(torch.arange(S, device=dev, dtype=torch.float32) + 2.0)
+        for label_name, n_grades in (("binary 5%", 2), ("4 grades", 4)):
+            if n_grades == 2:
+                labels = (torch.rand(B, S, device=dev, generator=g) < 0.05).float()
+            else:
+                labels = torch.randint(0, 4, (B, S), device=dev, generator=g).float()
+            gains = (2.0 ** labels) - 1.0
+            for kind in ("ranknet", "lambdarank"):
+                def fused():
+                    s = score.clone().requires_grad_(True)
+                    ops.PairRankLossFn.apply(s, labels, kind, 1.0, None, n_grades, False).backward()
+                    return s.grad
+
+                def composed():
+                    grad = torch.empty_like(score)
+                    for lo in range(0, B, tile):
+                        s = score[lo:lo + tile].clone().requires_grad_(True)
+                        y, G = labels[lo:lo + tile], gains[lo:lo + tile]
+                        pair = y[:, :, None] > y[:, None, :]
+                        l = torch.nn.functional.softplus(-(s[:, :, None] - s[:, None, :]))
+                        if kind == "lambdarank":
+                            rank = torch.argsort(torch.argsort(s.detach(), dim=1, descending=True, stable=True), dim=1)
+                            D = disc[rank]
+                            w = (G[:, :, None] - G[:, None, :]).abs() * (D[:, :, None] - D[:, None, :]).abs()
+                            per = (l * w * pair).sum(dim=(1, 2))
+                        else:
+                            per = (l * pair).sum(dim=(1, 2)) / pair.sum(dim=(1, 2)).clamp(min=1)
+                        (per.sum() / B).backward()
+                        grad[lo:lo + tile] = s.grad
+                    return grad
+
+                def hinge():
+                    s = score.clone().requires_grad_(True)
+                    ops.RerankLossFn.apply(s, labels.clamp(max=1.0), 5e-4).backward()
+                    return s.grad
+                a, b = fused(), composed()
+                err = float((a - b).abs().max() / b.abs().max().clamp(min=1e-30))
+                del a, b
+                torch.cuda.empty_cache()
+                for r in range(runs):
+                    med = {name: median_ms(fn) for name, fn in (("rlt_pair_rank_loss", fused), ("tiled torch composition", composed),
+                                                                 ("rlt_mt_terms + _bwd (hinge)", hinge))}
+                    for name, ms in med.items():
+                        print(f"pair_rank B{B} S{S} {label_name:10s} {kind:10s} run {r} {name:30s}: {ms * 1e3:10.1f} us  "
+                              f"{B * S * S / ms / 1e6:8.2f} G pair visits/s", flush=True)
+                    print(f"pair_rank B{B} S{S} {label_name:10s} {kind:10s} run {r} torch / kernel {med['tiled torch composition'] / med['rlt_pair_rank_loss']:.1f}x, "
+                          f"kernel / hinge {med['rlt_pair_rank_loss'] / med['rlt_mt_terms + _bwd (hinge)']:.1f}x, "
+                          f"max |kernel - torch| / max |torch| = {err:.1e}", flush=True)
+                    torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
