@@ -726,13 +726,35 @@ int rlt_attention_dropout_mask_range(uint32_t seed, int pair0, int npair, int B,
  * the index limits above), RLT_E_ALIGN (a pointer off 16 bytes), RLT_E_WORKSPACE (ws_bytes below the query's answer).
  * Algorithmic bytes: fwd reads 12*S*B*E (qkv) and writes 4*S*B*E + 4*B*H*S; bwd reads 12*S*B*E + 8*S*B*E + 4*B*H*S and writes
  * 12*S*B*E (K / V - in the backward also Q / dO - tiles are re-read once per 128 owned rows at head dim 64, per 32 at head
- * dim 16, from L2). */
+ * dim 16, from L2).
+ * The mask (rlt_seq_attention_fwd_ex / _bwd_ex; the calls without _ex are the _ex calls with RLT_SEQ_MASK_NONE, same launches,
+ * same bits): RLT_SEQ_MASK_NONE admits every key of the list for every query; RLT_SEQ_MASK_CAUSAL admits key j for query i
+ * iff j <= i, so out, lse and - for a dout that is zero from position i on - dqkv of the positions < i do not depend on
+ * the rows of positions >= i: bit for bit for finite inputs (tests/test_seq_causal_gpu.py against tests/seq_causal_restate.py).
+ *   lse is the log-normaliser over the ADMITTED keys; delta = rowsum(dout * out) as before.  Row 0 admits key 0 alone: its
+ *   weight is exactly 1, and without dropout out at position 0 IS V at position 0, bit for bit.
+ *   dropout: the keep stream stays keyed by (pair, query, key) - a masked element's draw is simply never used, and the kept
+ *   elements of a causal call are those of the unmasked call at the same (drop_p, seed).
+ *   NOT isolated: non-finite values below a row.  A masked weight is an exact 0 multiplied into the K, V, Q or dO row of the
+ *   same 32-row sub-tile, and 0 * NaN = 0 * inf = NaN: a NaN or inf planted BELOW position i can reach row i when both lie
+ *   in one 32-position block (or, in the backward, one 32-query block that a key's wavefront visits).  Finite values never do.
+ *   the kernels skip the 32 x 32 tiles above the diagonal (forward and both backward phases: t + 1 of the products of
+ *   32-row block t) and do not stage the 64-row tiles no wavefront of the pass needs.  The algorithmic bytes are those above,
+ *   unchanged: every row is still read and written once; only the L2 tile re-reads fall.
+ *   a mask code outside {0, 1} is RLT_E_ARG, with the other argument errors and ahead of RLT_E_SHAPE / _ALIGN / _WORKSPACE. */
+#define RLT_SEQ_MASK_NONE   0
+#define RLT_SEQ_MASK_CAUSAL 1
 size_t rlt_seq_attention_bwd_workspace(int S, int B, int H, int HD, float drop_p, int precision);   /* may be 0 */
 int rlt_seq_attention_fwd(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed,
                           float* out, float* lse, int precision, void* stream);
 int rlt_seq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
                           int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv,
                           void* ws, size_t ws_bytes, int precision, void* stream);
+int rlt_seq_attention_fwd_ex(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed, int mask,
+                             float* out, float* lse, int precision, void* stream);
+int rlt_seq_attention_bwd_ex(const float* qkv, const float* out, const float* dout, const float* lse,
+                             int S, int B, int H, int HD, float drop_p, uint32_t seed, int mask, float* dqkv,
+                             void* ws, size_t ws_bytes, int precision, void* stream);
 
 /* ------------------------------------------------------------------ BiLSTM recurrence (M2)
  * One bidirectional LSTM layer with hidden size 128 (nn.LSTM(..., hidden_size=128,

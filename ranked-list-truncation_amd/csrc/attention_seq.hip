@@ -20,6 +20,12 @@
 // (scores and dP are recomputed in both phases: 7 products of 4*S*S*HD/2 flops per (list, head) instead of 5).
 // The three precision codes run these same kernels (exact fp32 is at least what bf16x6 / bf16x3 promise).
 // Dropout: stream pair_seed(seed, b*H + h), keep = rlt_keep(stream, query, key, thr), kept weights * 1/(1-p).
+// CAUSAL (rlt_seq_attention_fwd_ex / _bwd_ex, RLT_SEQ_MASK_CAUSAL): key j is admitted for query i iff j <= i.  A compare per score in
+// the diagonal sub-tile, and the tiles above the diagonal are skipped: the forward and phase 1 end the key-tile loop at the pass's
+// last query (block-uniform) and a wavefront leaves the sub-tile loop behind its own last query; phase 2 starts the query-tile
+// loop at the pass's first key and a wavefront skips the sub-tiles in front of its own.  lse is over the admitted keys; the keep
+// stream is unchanged (a masked draw is never used).  A masked weight is an exact 0 times a row of the same sub-tile: finite rows
+// below a position never reach it, a NaN or inf there can.  The CAUSAL = false instantiations are the kernels as they were.
 #include "attention_common.h"
 
 namespace {
@@ -99,6 +105,12 @@ __device__ __forceinline__ void sq_store_T(float* __restrict__ dst, int hh, cons
     store_acc_T<HD>(dst, hh, acc, mul);
 }
 
+// the last key tile a pass of queries [.., qend) needs under the causal mask ends at its last query
+__device__ __forceinline__ int sq_key_end(int S, int qend) { return qend < S ? qend : S; }
+
+// the causal mask: key `key` is admitted for query `q` iff it lies inside the list and not behind the query
+__device__ __forceinline__ bool sq_admit(int key, int q, int S) { return key < S && key <= q; }
+
 template <int HD>
 struct SeqGeom {
     static constexpr int HPG = 64 / HD;           // heads per workgroup
@@ -107,7 +119,7 @@ struct SeqGeom {
     static constexpr int KH = HD / 2;             // columns of a head per lane half
 };
 
-template <int HD, bool DROP>
+template <int HD, bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqArgs a) {
     using G = SeqGeom<HD>;
     constexpr int HPG = G::HPG, OWN = G::OWN, DT = G::DT, KH = G::KH;
@@ -144,7 +156,8 @@ __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqArgs a) {
         float m = -INFINITY, lsum = 0.f;
         const uint32_t rh = DROP ? rlt_row_hash(stream, (uint32_t)q) : 0u;
 
-        for (int k0 = 0; k0 < S; k0 += SQ_TR) {
+        const int kend = CAUSAL ? sq_key_end(S, q0 + OWN) : S;      // block-uniform: staging is collective
+        for (int k0 = 0; k0 < kend; k0 += SQ_TR) {
             __syncthreads();
             sq_stage(Ks, a.qkv + E, ld, B, b, k0, S, c0, cw, tid);
             sq_stage(Vs, a.qkv + 2 * (size_t)E, ld, B, b, k0, S, c0, cw, tid);
@@ -155,16 +168,17 @@ __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqArgs a) {
             for (int sub = 0; sub < SQ_TR / 32; ++sub) {
                 const int kb = k0 + 32 * sub;
                 if (kb >= S) break;
+                if (CAUSAL && kb > q0 + woff + 31) break;   // every key of the sub-tile lies behind the wavefront's last query
                 // S^T[key][query]: register r of this lane = key kb + acc_row(r, hh), query q
                 f32x16 s = sq_rows_dot<KH>(Ks + (32 * sub + l31) * SQ_LD + hc + hh * KH, qr);
                 float mx = m;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float sv = kb + acc_row(r, hh) < S ? s[r] * c : -INFINITY;
+                    const float sv = (CAUSAL ? sq_admit(kb + acc_row(r, hh), q, S) : kb + acc_row(r, hh) < S) ? s[r] * c : -INFINITY;
                     s[r] = sv;
                     mx = fmaxf(mx, sv);
                 }
-                mx = fmaxf(mx, __shfl_xor(mx, 32));          // key kb itself is < S: finite from the first tile on
+                mx = fmaxf(mx, __shfl_xor(mx, 32));          // key kb itself is < S: finite from the first tile on (causal: key 0)
                 const float alpha = rlt_exp2(m - mx);
                 m = mx;
                 lsum *= alpha;
@@ -201,7 +215,7 @@ size_t seq_bwd_lds_bytes(int S) {
     return sizeof(float) * (2 * (size_t)SQ_TR * SQ_LD + 2 * G::HPG * Sr + (size_t)G::HPG * SQ_TR);
 }
 
-template <int HD, bool DROP>
+template <int HD, bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
     using G = SeqGeom<HD>;
     constexpr int HPG = G::HPG, OWN = G::OWN, DT = G::DT, KH = G::KH;
@@ -259,7 +273,8 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
             for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
         const uint32_t rh = DROP ? rlt_row_hash(stream, (uint32_t)q) : 0u;
 
-        for (int k0 = 0; k0 < S; k0 += SQ_TR) {
+        const int kend = CAUSAL ? sq_key_end(S, q0 + OWN) : S;
+        for (int k0 = 0; k0 < kend; k0 += SQ_TR) {
             __syncthreads();
             sq_stage(Xs, a.qkv + E, ld, B, b, k0, S, c0, cw, tid);                    // K
             sq_stage(Ys, a.qkv + 2 * (size_t)E, ld, B, b, k0, S, c0, cw, tid);        // V
@@ -270,12 +285,13 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
             for (int sub = 0; sub < SQ_TR / 32; ++sub) {
                 const int kb = k0 + 32 * sub;
                 if (kb >= S) break;
+                if (CAUSAL && kb > q0 + woff + 31) break;
                 const int trow = (32 * sub + l31) * SQ_LD + hc + hh * KH;
                 f32x16 s = sq_rows_dot<KH>(Xs + trow, qr);            // S^T[key][query]
                 f32x16 dp = sq_rows_dot<KH>(Ys + trow, dor);          // dP^T[key][query]
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float p = kb + acc_row(r, hh) < S ? rlt_exp2(s[r] * c - lse2) : 0.f;
+                    const float p = (CAUSAL ? sq_admit(kb + acc_row(r, hh), q, S) : kb + acc_row(r, hh) < S) ? rlt_exp2(s[r] * c - lse2) : 0.f;
                     float g = dp[r];
                     if (DROP) g = rlt_keep_rc(rh, hash_w[32 * sub + acc_row(r, hh)], a.thr) ? g * a.inv_keep : 0.f;
                     s[r] = p * (g - delta) * a.scale;                 // dS^T, with the score scale
@@ -305,7 +321,8 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
             for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
         const uint32_t ch = DROP ? rlt_col_hash(stream, (uint32_t)key) : 0u;
 
-        for (int q0 = 0; q0 < S; q0 += SQ_TR) {
+        // causal: the queries in front of the pass's first key weigh it 0 - start at the 64-row tile that holds that key
+        for (int q0 = CAUSAL ? k0 / SQ_TR * SQ_TR : 0; q0 < S; q0 += SQ_TR) {
             __syncthreads();                                                           // also: phase 1's lse2 / delta are complete
             sq_stage(Xs, a.qkv, ld, B, b, q0, S, c0, cw, tid);                         // Q
             sq_stage(Ys, a.dout, (size_t)E, B, b, q0, S, c0, cw, tid);                 // dO
@@ -316,6 +333,7 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
             for (int sub = 0; sub < SQ_TR / 32; ++sub) {
                 const int qb = q0 + 32 * sub;
                 if (qb >= S) break;
+                if (CAUSAL && qb + 31 < k0 + woff) continue;          // every query of the sub-tile lies in front of the wavefront's first key
                 const int trow = (32 * sub + l31) * SQ_LD + hc + hh * KH;
                 f32x16 s = sq_rows_dot<KH>(Xs + trow, kr);            // S[query][key]: register r = query qb + acc_row(r, hh)
                 f32x16 dp = sq_rows_dot<KH>(Ys + trow, vr);           // dP[query][key]
@@ -323,6 +341,7 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqArgs a) {
                 for (int r = 0; r < 16; ++r) {
                     const int qq = qb + acc_row(r, hh);               // < Sr; rows >= S have lse2 = +inf: weight 0
                     float p = rlt_exp2(s[r] * c - lse2_w[qq]);
+                    if (CAUSAL) p = qq >= key ? p : 0.f;              // selected, not left to lse
                     float g = dp[r];
                     if (DROP) {
                         const bool keep = rlt_keep_rc(hash_w[32 * sub + acc_row(r, hh)], ch, a.thr);
@@ -371,25 +390,34 @@ SeqArgs seq_args(int S, int B, int H, int HD, float drop_p, uint32_t seed) {
     return a;
 }
 
-template <int HD>
-int seq_launch_fwd(const SeqArgs& a, bool drop, hipStream_t st) {
+template <int HD, bool DROP, bool CAUSAL>
+int seq_launch_fwd_as(const SeqArgs& a, hipStream_t st) {
     const int ngrp = (a.H + SeqGeom<HD>::HPG - 1) / SeqGeom<HD>::HPG;
     const dim3 grid((unsigned)((long long)a.B * ngrp)), block(256);
-    if (drop) hipLaunchKernelGGL((seq_attn_fwd_kernel<HD, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((seq_attn_fwd_kernel<HD, false>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((seq_attn_fwd_kernel<HD, DROP, CAUSAL>), grid, block, 0, st, a);
+    return RLT_LAUNCH_RESULT();
+}
+
+template <int HD, bool DROP, bool CAUSAL>
+int seq_launch_bwd_as(const SeqArgs& a, hipStream_t st) {
+    const int ngrp = (a.H + SeqGeom<HD>::HPG - 1) / SeqGeom<HD>::HPG;
+    const dim3 grid((unsigned)((long long)a.B * ngrp)), block(256);
+    const size_t lds = seq_bwd_lds_bytes<HD>(a.S);
+    if (int rc = rlt_allow_lds(seq_attn_bwd_kernel<HD, DROP, CAUSAL>, lds)) return rc;
+    hipLaunchKernelGGL((seq_attn_bwd_kernel<HD, DROP, CAUSAL>), grid, block, lds, st, a);
     return RLT_LAUNCH_RESULT();
 }
 
 template <int HD>
-int seq_launch_bwd(const SeqArgs& a, bool drop, hipStream_t st) {
-    const int ngrp = (a.H + SeqGeom<HD>::HPG - 1) / SeqGeom<HD>::HPG;
-    const dim3 grid((unsigned)((long long)a.B * ngrp)), block(256);
-    const size_t lds = seq_bwd_lds_bytes<HD>(a.S);
-    int rc = drop ? rlt_allow_lds(seq_attn_bwd_kernel<HD, true>, lds) : rlt_allow_lds(seq_attn_bwd_kernel<HD, false>, lds);
-    if (rc) return rc;
-    if (drop) hipLaunchKernelGGL((seq_attn_bwd_kernel<HD, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((seq_attn_bwd_kernel<HD, false>), grid, block, lds, st, a);
-    return RLT_LAUNCH_RESULT();
+int seq_launch_fwd(const SeqArgs& a, bool drop, bool causal, hipStream_t st) {
+    if (causal) return drop ? seq_launch_fwd_as<HD, true, true>(a, st) : seq_launch_fwd_as<HD, false, true>(a, st);
+    return drop ? seq_launch_fwd_as<HD, true, false>(a, st) : seq_launch_fwd_as<HD, false, false>(a, st);
+}
+
+template <int HD>
+int seq_launch_bwd(const SeqArgs& a, bool drop, bool causal, hipStream_t st) {
+    if (causal) return drop ? seq_launch_bwd_as<HD, true, true>(a, st) : seq_launch_bwd_as<HD, false, true>(a, st);
+    return drop ? seq_launch_bwd_as<HD, true, false>(a, st) : seq_launch_bwd_as<HD, false, false>(a, st);
 }
 
 }  // namespace
@@ -402,22 +430,31 @@ size_t rlt_seq_attention_bwd_workspace(int S, int B, int H, int HD, float drop_p
     return 0;          // dQ, dK and dV are finished inside one workgroup: nothing to stage, nothing to sum
 }
 
-int rlt_seq_attention_fwd(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed,
-                          float* out, float* lse, int precision, void* stream) {
+int rlt_seq_attention_fwd_ex(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed, int mask,
+                             float* out, float* lse, int precision, void* stream) {
     RLT_PREC_SCOPE(precision);
     RLT_CHECK_ARG(qkv && out && lse);
+    RLT_CHECK_ARG(mask == RLT_SEQ_MASK_NONE || mask == RLT_SEQ_MASK_CAUSAL);
     if (int rc = seq_check_dims(S, B, H, HD, drop_p)) return rc;
     if (!rlt_aligned16(qkv) || !rlt_aligned16(out) || !rlt_aligned16(lse)) return RLT_E_ALIGN;
     SeqArgs a = seq_args(S, B, H, HD, drop_p, seed);
     a.qkv = qkv; a.o = out; a.lse_o = lse;
-    return HD == 64 ? seq_launch_fwd<64>(a, drop_p > 0.f, rlt_stream(stream)) : seq_launch_fwd<16>(a, drop_p > 0.f, rlt_stream(stream));
+    const bool causal = mask == RLT_SEQ_MASK_CAUSAL;
+    return HD == 64 ? seq_launch_fwd<64>(a, drop_p > 0.f, causal, rlt_stream(stream))
+                    : seq_launch_fwd<16>(a, drop_p > 0.f, causal, rlt_stream(stream));
 }
 
-int rlt_seq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
-                          int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv,
-                          void* ws, size_t ws_bytes, int precision, void* stream) {
+int rlt_seq_attention_fwd(const float* qkv, int S, int B, int H, int HD, float drop_p, uint32_t seed,
+                          float* out, float* lse, int precision, void* stream) {
+    return rlt_seq_attention_fwd_ex(qkv, S, B, H, HD, drop_p, seed, RLT_SEQ_MASK_NONE, out, lse, precision, stream);
+}
+
+int rlt_seq_attention_bwd_ex(const float* qkv, const float* out, const float* dout, const float* lse,
+                             int S, int B, int H, int HD, float drop_p, uint32_t seed, int mask, float* dqkv,
+                             void* ws, size_t ws_bytes, int precision, void* stream) {
     RLT_PREC_SCOPE(precision);
     RLT_CHECK_ARG(qkv && out && dout && lse && dqkv);
+    RLT_CHECK_ARG(mask == RLT_SEQ_MASK_NONE || mask == RLT_SEQ_MASK_CAUSAL);
     if (int rc = seq_check_dims(S, B, H, HD, drop_p)) return rc;
     if (!rlt_aligned16(qkv) || !rlt_aligned16(out) || !rlt_aligned16(dout) || !rlt_aligned16(lse) || !rlt_aligned16(dqkv) ||
         !rlt_aligned16(ws))
@@ -425,7 +462,16 @@ int rlt_seq_attention_bwd(const float* qkv, const float* out, const float* dout,
     if (ws_bytes < rlt_seq_attention_bwd_workspace(S, B, H, HD, drop_p, precision)) return RLT_E_WORKSPACE;   // 0 bytes: ws may be NULL
     SeqArgs a = seq_args(S, B, H, HD, drop_p, seed);
     a.qkv = qkv; a.out = out; a.dout = dout; a.lse = lse; a.dqkv = dqkv;
-    return HD == 64 ? seq_launch_bwd<64>(a, drop_p > 0.f, rlt_stream(stream)) : seq_launch_bwd<16>(a, drop_p > 0.f, rlt_stream(stream));
+    const bool causal = mask == RLT_SEQ_MASK_CAUSAL;
+    return HD == 64 ? seq_launch_bwd<64>(a, drop_p > 0.f, causal, rlt_stream(stream))
+                    : seq_launch_bwd<16>(a, drop_p > 0.f, causal, rlt_stream(stream));
+}
+
+int rlt_seq_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
+                          int S, int B, int H, int HD, float drop_p, uint32_t seed, float* dqkv,
+                          void* ws, size_t ws_bytes, int precision, void* stream) {
+    return rlt_seq_attention_bwd_ex(qkv, out, dout, lse, S, B, H, HD, drop_p, seed, RLT_SEQ_MASK_NONE, dqkv, ws, ws_bytes, precision,
+                                    stream);
 }
 
 }  // extern "C"

@@ -51,9 +51,10 @@ class TowerRerank(_Tower):
 
 class MMOECut(C.CutModel):
     def __init__(self, seq_len: int = 300, num_experts=3, num_tasks=3, input_size=3, encoding_size=128,
-                 d_model=256, n_head=4, num_layers=1, dropout=0.2, attention_axis="list"):
+                 d_model=256, n_head=4, num_layers=1, dropout=0.2, attention_axis="list", attention_mask="none"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
+        self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
         if d_model != 2 * encoding_size:
             # the reference fails later, inside the first expert (models/MMOECut.py:88-90: the experts take the BiLSTM's
             # 2*encoding_size outputs as d_model inputs); say so at construction
@@ -86,7 +87,7 @@ class MMOECut(C.CutModel):
         if S != self.seq_len:
             raise ValueError(f"MMOECut was built for seq_len={self.seq_len}, got {S}")
         h = C.bilstm(ops.to_position_major(x), self.pre_encoding, S, B)                  # (S*B, 256)
-        expert_out = [C.encoder(h, e.attention_layer, self.n_head, S, B, drop_p, self.attention_axis) for e in self.experts]
+        expert_out = [C.encoder(h, e.attention_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal") for e in self.experts]
         gates = ops.MMOEGateFn.apply(h, S, B, *self.w_gates)                              # (n_tasks,B,n_e)
         mixed = ops.MMOEMixFn.apply(gates, S, B, *expert_out)                             # (n_tasks,S*B,E)
         outs = []

@@ -8,9 +8,10 @@ from ._mt import mt_heads
 
 class MtAttnCut(C.CutModel):
     def __init__(self, input_size: int = 3, d_model: int = 256, n_head: int = 4, num_layers: int = 1,
-                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list"):
+                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
+        self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
         self.num_tasks, self.n_head, self.dropout = num_tasks, n_head, dropout
         self.pre_encoding = C.bilstm_params(input_size)
         self.encoding_layer = C.encoder_params(d_model, n_head, num_layers, dropout)
@@ -23,5 +24,5 @@ class MtAttnCut(C.CutModel):
         drop_p = C.check_dropout(self, self.dropout)
         B, S, _ = x.shape
         h = C.bilstm(ops.to_position_major(x), self.pre_encoding, S, B)
-        h = C.encoder(h, self.encoding_layer, self.n_head, S, B, drop_p, self.attention_axis)
+        h = C.encoder(h, self.encoding_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal")
         return mt_heads(self, h, S, B)

@@ -9,9 +9,10 @@ from ._mt import mt_heads
 
 class MtChoopy(C.CutModel):
     def __init__(self, seq_len: int = 300, d_model: int = 128, n_head: int = 8, num_layers: int = 3,
-                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list"):
+                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
+        self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
         self.seq_len, self.num_tasks, self.n_head, self.dropout = seq_len, num_tasks, n_head, dropout
         self.position_encoding = nn.Parameter(torch.randn(seq_len, 127), requires_grad=True)
         self.encoding_layer = C.encoder_params(d_model, n_head, num_layers, dropout)
@@ -26,5 +27,5 @@ class MtChoopy(C.CutModel):
         if S != self.seq_len:
             raise ValueError(f"MtChoopy was built for seq_len={self.seq_len}, got {S}")
         h = ops.choopy_embed(x, self.position_encoding)
-        h = C.encoder(h, self.encoding_layer, self.n_head, S, B, drop_p, self.attention_axis)
+        h = C.encoder(h, self.encoding_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal")
         return mt_heads(self, h, S, B)

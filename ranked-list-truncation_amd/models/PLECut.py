@@ -10,9 +10,10 @@ from .MMOECut import Expert, TowerClass, TowerCut, TowerRerank
 
 class PLECut(C.CutModel):
     def __init__(self, seq_len: int = 300, num_experts=3, input_size=3, encoding_size=128, d_model=256, n_head=2,
-                 num_layers=1, dropout=0.1, attention_axis="list"):
+                 num_layers=1, dropout=0.1, attention_axis="list", attention_mask="none"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
+        self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
         if d_model != 2 * encoding_size:
             raise ValueError(f"d_model ({d_model}) must equal 2 * encoding_size ({2 * encoding_size})")
         if num_experts != 3:
@@ -31,7 +32,7 @@ class PLECut(C.CutModel):
         if S != self.seq_len:
             raise ValueError(f"PLECut was built for seq_len={self.seq_len}, got {S}")
         h = C.bilstm(ops.to_position_major(x), self.pre_encoding, S, B)
-        eo = [C.encoder(h, e.attention_layer, self.n_head, S, B, drop_p, self.attention_axis) for e in self.experts]
+        eo = [C.encoder(h, e.attention_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal") for e in self.experts]
         groups = [eo[:2], eo[1:], eo]                                                     # models/PLECut.py:80-82
         outs = []
         for w_gate, grp, tower in zip(self.w_gates, groups, self.towers):

@@ -15,9 +15,9 @@ class ProbeBase(MMOECut):
     reference's zip gives), batch-major views of the position-major tensors forward_pm returns."""
 
     def __init__(self, seq_len: int = 300, num_experts=2, num_tasks=3, input_size=3, encoding_size=128, d_model=256,
-                 n_head=4, num_layers=1, dropout=0.2, attention_axis="list"):
+                 n_head=4, num_layers=1, dropout=0.2, attention_axis="list", attention_mask="none"):
         super().__init__(seq_len, num_experts, num_tasks, input_size, encoding_size, d_model, n_head, num_layers, dropout,
-                         attention_axis)
+                         attention_axis, attention_mask)
         if num_tasks != 3:
             self.towers = nn.ModuleList([TowerClass(d_model), TowerRerank(d_model), TowerCut(d_model)])
 

@@ -73,13 +73,23 @@ def check_attention_axis(axis):
     return ops.check_attention_axis(axis)
 
 
-def encoder(x_pm, params, n_head, S, B, drop_p=0.0, axis="list"):
+def check_attention_mask(mask, axis):
+    """'none' (every position attends to every position of its list) or 'causal' (position i attends to the positions <= i: the
+    encoder's output at rank i is computed without looking below rank i); 'causal' needs axis 'position', anything else is a
+    ValueError.  Like the axis, the mask changes no parameter: state_dicts load across masks.  -> the mask string."""
+    ops.check_attention_mask(mask, axis)
+    return mask
+
+
+def encoder(x_pm, params, n_head, S, B, drop_p=0.0, axis="list", causal=False):
     """Stack of post-norm encoder layers with list-axis (axis='list') or within-list (axis='position') attention.  drop_p > 0
     applies the four dropouts of nn.TransformerEncoderLayer: attention probabilities, dropout1 (attention branch),
-    the FFN hidden dropout and dropout2 (FFN branch)."""
+    the FFN hidden dropout and dropout2 (FFN branch).  causal=True (axis='position' only, else ValueError): every layer attends
+    to the positions <= i, and since the rest of a layer is per row, row i of the stack's output depends on rows <= i of x_pm."""
+    ops.check_attention_mask("causal" if causal else "none", axis)
     h = x_pm
     for layer in params.layers.children():
-        h = ops.encoder_layer(h, layer, S, B, n_head, drop_p, axis=axis)
+        h = ops.encoder_layer(h, layer, S, B, n_head, drop_p, axis=axis, causal=causal)
     return h
 
 

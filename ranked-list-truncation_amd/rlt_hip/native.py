@@ -24,6 +24,7 @@ SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE = 0, 1, 2
 SWEEP_COLS, SWEEP_MAX_T = 8, 64
 REWARD_FBETA, REWARD_GAIN, REWARD_MAX_GRADES = 0, 1, 8
 PAIR_RANKNET, PAIR_LAMBDARANK = 0, 1
+SEQ_MASK_NONE, SEQ_MASK_CAUSAL = 0, 1
 PAIR_KINDS = {"ranknet": PAIR_RANKNET, "lambdarank": PAIR_LAMBDARANK}
 SWEEP_ROWS = ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut", "n_lists")      # the rows of rlt_cut_sweep's curve
 PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
@@ -114,6 +115,8 @@ _SIGNATURES = {
     "rlt_seq_attention_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_float, c_int]),
     "rlt_seq_attention_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_int, P]),
     "rlt_seq_attention_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_size_t, c_int, P]),
+    "rlt_seq_attention_fwd_ex": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_int, P]),
+    "rlt_seq_attention_bwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_size_t, c_int, P]),
     "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),

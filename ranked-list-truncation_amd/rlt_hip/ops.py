@@ -309,34 +309,43 @@ def list_attention(qkv, S, B, H, drop_p=0.0):
 
 
 # ------------------------------------------------------------------------------ within-list ("position-axis") attention
-def _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr):
+def _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr, causal=False):
     out = _empty((S * B, H * HD), qkv)
     lse = _empty((B, H, S), qkv)
-    _launch("seq_attn_fwd", lambda: call("rlt_seq_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, seed, ptr(out), ptr(lse), pr, stream()))
+    if causal:
+        _launch("seq_attn_fwd", lambda: call("rlt_seq_attention_fwd_ex", ptr(qkv), S, B, H, HD, drop_p, seed, N.SEQ_MASK_CAUSAL,
+                                             ptr(out), ptr(lse), pr, stream()))
+    else:
+        _launch("seq_attn_fwd", lambda: call("rlt_seq_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, seed, ptr(out), ptr(lse), pr, stream()))
     return out, lse
 
 
-def _seq_attention_bwd(qkv, out, dout, lse, S, B, H, HD, drop_p, seed, pr):
+def _seq_attention_bwd(qkv, out, dout, lse, S, B, H, HD, drop_p, seed, pr, causal=False):
     dqkv = torch.empty_like(qkv)
     ws_bytes = query("rlt_seq_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
     ws = workspace(ws_bytes, qkv.device) if ws_bytes else None
-    _launch("seq_attn_bwd", lambda: call("rlt_seq_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, seed,
-                                         ptr(dqkv), ptr(ws), ws_bytes, pr, stream()))
+    if causal:
+        _launch("seq_attn_bwd", lambda: call("rlt_seq_attention_bwd_ex", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, seed,
+                                             N.SEQ_MASK_CAUSAL, ptr(dqkv), ptr(ws), ws_bytes, pr, stream()))
+    else:
+        _launch("seq_attn_bwd", lambda: call("rlt_seq_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, seed,
+                                             ptr(dqkv), ptr(ws), ws_bytes, pr, stream()))
     return dqkv
 
 
 class SeqAttentionFn(Function):
     """qkv (S*B, 3E) -> concatenated heads (S*B, E); every list attends over its own S positions (rlt_seq_attention_*: one
-    launch forward, one launch backward)."""
+    launch forward, one launch backward).  causal: position i attends to the positions <= i only (RLT_SEQ_MASK_CAUSAL)."""
 
     @staticmethod
-    def forward(ctx, qkv, S, B, H, drop_p=0.0, seed=0):
+    def forward(ctx, qkv, S, B, H, drop_p=0.0, seed=0, causal=False):
         E = qkv.shape[1] // 3
         if qkv.shape != (S * B, 3 * E) or E % H:
             raise RuntimeError(f"seq_attention: qkv {tuple(qkv.shape)} does not match S*B = {S * B} rows of 3 * H * HD columns")
         HD = E // H
         ctx.prec = pr = current_precision()
-        out, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr)
+        ctx.causal = bool(causal)
+        out, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr, ctx.causal)
         ctx.dims = (S, B, H, HD)
         ctx.drop = (drop_p, seed)
         ctx.save_for_backward(qkv, out, lse)
@@ -347,13 +356,13 @@ class SeqAttentionFn(Function):
         qkv, out, lse = ctx.saved_tensors
         S, B, H, HD = ctx.dims
         drop_p, seed = ctx.drop
-        dqkv = _seq_attention_bwd(qkv, out, N.f32c(dout), lse, S, B, H, HD, drop_p, seed, ctx.prec)
-        return dqkv, None, None, None, None, None
+        dqkv = _seq_attention_bwd(qkv, out, N.f32c(dout), lse, S, B, H, HD, drop_p, seed, ctx.prec, ctx.causal)
+        return dqkv, None, None, None, None, None, None
 
 
-def seq_attention(qkv, S, B, H, drop_p=0.0):
+def seq_attention(qkv, S, B, H, drop_p=0.0, causal=False):
     N.require_cuda(qkv)
-    return SeqAttentionFn.apply(N.f32c(qkv), S, B, H, drop_p, next_seed() if drop_p > 0 else 0)
+    return SeqAttentionFn.apply(N.f32c(qkv), S, B, H, drop_p, next_seed() if drop_p > 0 else 0, causal)
 
 
 # ------------------------------------------------------------------------------ whole encoder layer
@@ -420,7 +429,7 @@ class EncoderLayerKernelsFn(Function):
     @staticmethod
     def forward(ctx, *args):
         ctx.prec = current_precision()
-        ctx.axis = "list"
+        ctx.axis, ctx.causal = "list", False
         with precision(ctx.prec):          # every gemm() below reads the scope
             return EncoderLayerKernelsFn._forward(ctx, *args)
 
@@ -440,7 +449,7 @@ class EncoderLayerKernelsFn(Function):
         gemm(0, 1, T, 3 * E, E, x, E, in_w, E, qkv, 3 * E, bias=in_b)
         images = None
         if ctx.axis == "position":
-            att, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, s_attn, pr)
+            att, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, s_attn, pr, ctx.causal)
         else:
             att = _empty((T, E), x)
             lse = _empty((S, H, B), x)
@@ -517,7 +526,7 @@ class EncoderLayerKernelsFn(Function):
         gemm(0, 0, T, E, E, dr1, E, out_w, E, datt, E)
         # attention
         if ctx.axis == "position":
-            dqkv = _seq_attention_bwd(qkv, att, datt, lse, S, B, H, HD, drop_p, s_attn, pr)
+            dqkv = _seq_attention_bwd(qkv, att, datt, lse, S, B, H, HD, drop_p, s_attn, pr, ctx.causal)
         else:
             images = ctx.images
             dqkv = torch.empty_like(qkv)
@@ -546,7 +555,7 @@ class EncoderLayerSeqFn(Function):
     @staticmethod
     def forward(ctx, *args):
         ctx.prec = current_precision()
-        ctx.axis = "position"
+        ctx.axis, ctx.causal = "position", False
         with precision(ctx.prec):
             return EncoderLayerKernelsFn._forward(ctx, *args)
 
@@ -556,7 +565,21 @@ class EncoderLayerSeqFn(Function):
             return EncoderLayerKernelsFn._backward(ctx, dy)
 
 
+class EncoderLayerSeqCausalFn(EncoderLayerSeqFn):
+    """EncoderLayerSeqFn under the causal mask: position i attends to the positions <= i of its list (rlt_seq_attention_fwd_ex /
+    _bwd_ex with RLT_SEQ_MASK_CAUSAL); everything else of the layer is per row, so row i of the layer's output depends on the
+    rows <= i of its input only."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.prec = current_precision()
+        ctx.axis, ctx.causal = "position", True
+        with precision(ctx.prec):
+            return EncoderLayerKernelsFn._forward(ctx, *args)
+
+
 ATTENTION_AXES = ("list", "position")
+ATTENTION_MASKS = ("none", "causal")
 
 
 def check_attention_axis(axis):
@@ -565,14 +588,27 @@ def check_attention_axis(axis):
     return axis
 
 
-def encoder_layer(x, layer, S, B, H, drop_p=0.0, eps=1e-5, axis="list"):
+def check_attention_mask(mask, axis):
+    """'none' or 'causal'; the causal mask exists on the position axis only (on the list axis the keys are other lists, which
+    have no order).  -> True for 'causal'."""
+    if mask not in ATTENTION_MASKS:
+        raise ValueError(f"attention mask must be one of {ATTENTION_MASKS}, got {mask!r}")
+    if mask == "causal" and check_attention_axis(axis) != "position":
+        raise ValueError("attention mask 'causal' needs attention axis 'position' (the list axis attends across lists, not positions)")
+    return mask == "causal"
+
+
+def encoder_layer(x, layer, S, B, H, drop_p=0.0, eps=1e-5, axis="list", causal=False):
     """`layer`: a ParamTree mirror of nn.TransformerEncoderLayer.  axis='list': the lists of the mini-batch attend to each other at
-    every position (what the reference computes); axis='position': every list attends over its own positions."""
+    every position (what the reference computes); axis='position': every list attends over its own positions - with causal=True
+    position i over the positions <= i only (nn.TransformerEncoderLayer called with the upper-triangular src_mask)."""
     check_attention_axis(axis)
+    if causal and axis != "position":
+        raise ValueError("causal=True needs axis='position' (the list axis attends across lists, not positions)")
     att = layer.self_attn
     seeds = tuple(next_seed() for _ in range(4)) if drop_p > 0 else (0, 0, 0, 0)
     if axis == "position":
-        fn = EncoderLayerSeqFn
+        fn = EncoderLayerSeqCausalFn if causal else EncoderLayerSeqFn
     else:
         fn = EncoderLayerKernelsFn if (KernelTimer.active is not None or KERNEL_LEVEL_ENCODER[0]) else EncoderLayerFn
     return fn.apply(x, att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias,

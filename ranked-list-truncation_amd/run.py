@@ -93,6 +93,7 @@ class ScalarLog:
 
 class Trainer:
     attention_axis = "list"      # of a trainer a driver assembles by hand (verify_probe.py); __init__ sets the run's
+    attention_mask = "none"      # likewise
     rerank_by = None             # --rerank-eval, likewise
 
     def __init__(self, args):
@@ -155,6 +156,10 @@ class Trainer:
         # --attention-axis: 'list' (the reference: lists attend to each other) or 'position' (every list over its own positions);
         # the weights do not depend on it, so it is recorded beside them and a mismatch on loading is a warning, not an error
         self.attention_axis = axis = getattr(args, "attention_axis", "list")
+        # --attention-mask: 'none', or 'causal' on the position axis (position i attends to the positions <= i).  Recorded beside
+        # the axis, but only when it is 'causal': the files of a default run are byte for byte what they were
+        self.attention_mask = mask = getattr(args, "attention_mask", "none")
+        mask_kw = {"attention_mask": mask} if mask != "none" else {}
         # --rerank-loss: the loss of the rerank head inside MtCutLoss - the reference's batch-wide hinge, or a pairwise RankNet /
         # LambdaRank loss (utils.losses.PairwiseRankLoss); the default builds the criterion exactly as before
         rr_loss = getattr(args, "rerank_loss", "hinge")
@@ -166,30 +171,30 @@ class Trainer:
             self.model = BiCut(input_size=feat, dropout=args.dropout, sparse_input=self.sparse_bicut)
             self.criterion = losses.BiCutLoss(metric=args.criterion)
         elif name == 'choopy':                                                 # run.py:65-68
-            self.model = Choopy(seq_len=self.seq_len, dropout=args.dropout, attention_axis=axis)
+            self.model = Choopy(seq_len=self.seq_len, dropout=args.dropout, attention_axis=axis, **mask_kw)
             self.criterion = losses.ChoopyLoss(metric=args.criterion)
         elif name == 'attncut':                                                # run.py:69-75
-            self.model = AttnCut(input_size=feat, dropout=args.dropout, attention_axis=axis)
+            self.model = AttnCut(input_size=feat, dropout=args.dropout, attention_axis=axis, **mask_kw)
             self.criterion = losses.DivLoss(metric=args.criterion, div_type=args.div_type,
                                             augmented=args.augmented_reward)
         elif name == 'mtchoopy':                                               # run.py:76-79
-            self.model = MtChoopy(seq_len=self.seq_len, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
+            self.model = MtChoopy(seq_len=self.seq_len, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis, **mask_kw)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
                                               classi_weight=args.class_weight, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mtattncut':                                              # run.py:80-84
-            self.model = MtAttnCut(input_size=feat, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis)
+            self.model = MtAttnCut(input_size=feat, num_tasks=args.num_tasks, dropout=args.dropout, attention_axis=axis, **mask_kw)
             self.criterion = losses.MtCutLoss(metric=args.criterion, rerank_weight=args.rerank_weight,
                                               classi_weight=args.class_weight, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mmoecut':                                                # run.py:85-90 (num_experts exposed)
             self.model = MMOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat,
-                                 dropout=args.dropout, num_experts=args.num_experts, attention_axis=axis)
+                                 dropout=args.dropout, num_experts=args.num_experts, attention_axis=axis, **mask_kw)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'moecut':                                                 # run.py:91-96
             self.model = MOECut(seq_len=self.seq_len, num_tasks=args.num_tasks, input_size=feat, dropout=args.dropout,
-                                attention_axis=axis)
+                                attention_axis=axis, **mask_kw)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         elif name == 'mtple':                                                  # run.py:97-102
-            self.model = PLECut(seq_len=self.seq_len, input_size=feat, dropout=args.dropout, num_experts=3, attention_axis=axis)
+            self.model = PLECut(seq_len=self.seq_len, input_size=feat, dropout=args.dropout, num_experts=3, attention_axis=axis, **mask_kw)
             self.criterion = losses.MtCutLoss(metric=args.criterion, num_tasks=args.num_tasks, **rr_kw)
         else:
             raise ValueError(f"model {name!r} is outside the HIP hot path "
@@ -204,7 +209,7 @@ class Trainer:
         self.flat = FlatModel(self.model)
         self.flat.broadcast_params()
         if resume:
-            self._warn_axis(resume.get("attention_axis", "list"), args.resume)
+            self._warn_axis(resume.get("attention_axis", "list"), args.resume, resume.get("attention_mask", "none"))
             self.model.load_state_dict(resume["model"])         # in place: into the views of the flat bucket
         total_steps = max(1, args.epochs * len(self.train_loader))
         self.optimizer = FusedAdam(self.flat, lr=args.lr, weight_decay=args.weight_decay, **grad_guard_kwargs(args),   # run.py:104
@@ -382,15 +387,22 @@ class Trainer:
                                            "dcg": means["orig"]["dcg"], "dcg_rr": means["rr"]["dcg"], "lengths": summ}
         return summ
 
-    def _warn_axis(self, stored, path):
+    def _warn_axis(self, stored, path, stored_mask="none"):
         if stored != self.attention_axis:
             logging.warning('{} was written with --attention-axis {}; this run uses {} (the weights load, the model differs)'.format(
                 path, stored, self.attention_axis))
+        if stored_mask != self.attention_mask:
+            logging.warning('{} was written with --attention-mask {}; this run uses {} (the weights load, the model differs)'.format(
+                path, stored_mask, self.attention_mask))
+
+    def _mask_record(self):
+        """{'attention_mask': 'causal'} for a causal run, {} otherwise: a default run writes no new key"""
+        return {"attention_mask": self.attention_mask} if self.attention_mask != "none" else {}
 
     def save_model(self):
         os.makedirs(self.save_path, exist_ok=True)
         with open(os.path.join(self.save_path, '{}.pkl.meta.json'.format(self.model_name)), "w") as f:      # beside the state_dict
-            json.dump({"attention_axis": self.attention_axis}, f)
+            json.dump({"attention_axis": self.attention_axis, **self._mask_record()}, f)
         # clone: parameters are views of the flat bucket
         state = {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}
         torch.save(state, os.path.join(self.save_path, '{}.pkl'.format(self.model_name)))
@@ -403,7 +415,7 @@ class Trainer:
         state = {"model": {k: v.detach().clone().cpu() for k, v in self.model.state_dict().items()}, "optimizer": opt, "epoch": epoch,
                  "best_test_f1": self.best_test_f1, "best_test_dcg": self.best_test_dcg, "best_epoch": self.best_epoch,
                  "f1_record": self.f1_record, "dcg_record": self.dcg_record, "history": self.history,
-                 "attention_axis": self.attention_axis}
+                 "attention_axis": self.attention_axis, **self._mask_record()}
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         torch.save(state, path)
 
@@ -411,7 +423,8 @@ class Trainer:
         meta = self.model_path + '.meta.json'
         if os.path.exists(meta):
             with open(meta) as f:
-                self._warn_axis(json.load(f).get("attention_axis", "list"), self.model_path)
+                stored = json.load(f)
+                self._warn_axis(stored.get("attention_axis", "list"), self.model_path, stored.get("attention_mask", "none"))
         self.model.load_state_dict(torch.load(self.model_path, map_location=self.device))
         logging.info('The best model has beed loaded from {}\n'.format(self.model_path))
 
@@ -545,6 +558,8 @@ class Trainer:
         if spec is not None:                    # the reward the reward columns are in: compare_reports(metric='reward') checks it
             per_len["reward_spec"] = np.asarray(eval_reward_text(spec))
         per_len["attention_axis"] = np.asarray(self.attention_axis)
+        if self.attention_mask != "none":
+            per_len["attention_mask"] = np.asarray(self.attention_mask)
         if self.rerank_by and labelled:
             per_len["rerank_by"] = np.asarray(self.rerank_by)
         np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
@@ -777,6 +792,10 @@ def build_parser():
                    help="axis the encoder layers attend over: 'list' = the lists of a mini-batch attend to each other at every position "
                         "(the reference); 'position' = every list attends over its own positions (the papers' model; a list's cut "
                         "then does not depend on its batch).  Recorded in --history-json, --report-out and --save-state")
+    p.add_argument('--attention-mask', type=str, default='none', choices=('none', 'causal'),
+                   help="'causal' (needs --attention-axis position): position i attends to the positions <= i of its list, so the "
+                        "encoder's output at rank i does not look below rank i (Choopy's logits are then prefix-only; AttnCut's "
+                        "BiLSTM and every softmax over positions stay global).  Recorded beside the axis when it is 'causal'")
     p.add_argument('--history-json', type=str, default=None, help="rank 0 writes the per-epoch train / test means and the best / best-5 figures here")
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "
@@ -868,6 +887,8 @@ def main(argv=None):
         eval_reward_spec(args)
     except ValueError as e:
         parser.error(str(e))
+    if args.attention_mask == "causal" and args.attention_axis != "position":
+        parser.error("--attention-mask causal needs --attention-axis position (the list axis attends across lists, not positions)")
     # RLT_FORCE_DIST=1: initialise the process group (and run the step's collectives) even with one rank - the RCCL
     # rehearsal on a one-GPU box (rlt_hip/parallel.py)
     if (int(os.environ.get("WORLD_SIZE", "1")) > 1 or (FORCE_COLLECTIVES and "RANK" in os.environ)) and not dist.is_initialized():
@@ -899,7 +920,7 @@ def main(argv=None):
             fin = lambda v: v if v is not None and math.isfinite(v) else None     # -inf (no test epoch) is not valid JSON
             json.dump({"history": trainer.history, "best_f1": fin(trainer.best_test_f1), "best_dcg": fin(trainer.best_test_dcg),
                        "best5_f1": fin(trainer.best5_f1), "best5_dcg": fin(trainer.best5_dcg), "best_epoch": trainer.best_epoch,
-                       "world": trainer.world, "attention_axis": trainer.attention_axis, **({"baselines": trainer.baseline_results} if args.baselines else {}),
+                       "world": trainer.world, "attention_axis": trainer.attention_axis, **trainer._mask_record(), **({"baselines": trainer.baseline_results} if args.baselines else {}),
                        **({"eval_reward": {"spec": eval_reward_text(eval_reward_spec(args)),
                                            "report": getattr(trainer, "report_results", None),
                                            "cut_sweep": getattr(trainer, "sweep_results", None)}} if eval_reward_spec(args) else {})}, f)

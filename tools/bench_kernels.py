@@ -1309,6 +1309,130 @@ def seq_attention(shapes=((4096, 300, 4, 64), (8192, 300, 8, 16)), reps=7, runs=
             torch.cuda.empty_cache()
 
 
+SEQ_SHAPES = ((4096, 300, 4, 64), (8192, 300, 8, 16))
+
+
+def _seq_median_ms(fn, reps):
+    import statistics
+    fn()                                                         # warm-up: code objects, allocator
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def seq_attention_causal(shapes=SEQ_SHAPES, reps=7, runs=2, layer=True):
+    """Causal within-list attention (rlt_seq_attention_fwd_ex / _bwd_ex, RLT_SEQ_MASK_CAUSAL) at (B, S, H, HD): the median of `reps`
+    HIP-event timings in each of `runs` runs, forward and backward, of
+      the causal kernels; the non-causal kernels in the same process (the calls without _ex); the composition a user would otherwise
+      write in torch (permute to (B, H, S, HD), fp32 scaled_dot_product_attention(is_causal=True), permute back, autograd backward;
+      the permutes counted); one encoder-layer step (forward + backward) on the position axis with and without the mask.
+    The causal / non-causal share is printed beside what the tile count expects (the 32 x 32 products on and below the diagonal over
+    all of them: 55 / 100 at S = 300) - nothing here fixes a ratio in advance.
+    RLT_PARENT_LIB=<a library built from the parent commit>: it is loaded beside the product library and its rlt_seq_attention_fwd /
+    _bwd are timed in the same runs on the same buffers; this build's non-causal medians are compared with them, the margin being
+    the parent's own spread between its two runs."""
+    import ctypes
+    D = N.PRECISION_DEFAULT
+    mine, theirs = {}, {}
+    parent = os.environ.get("RLT_PARENT_LIB")
+    plib = ctypes.CDLL(os.path.abspath(parent)) if parent else None
+    for name in ("rlt_seq_attention_fwd", "rlt_seq_attention_bwd") if plib else ():
+        getattr(plib, name).restype, getattr(plib, name).argtypes = N._SIGNATURES[name]
+    for B, S, H, HD in shapes:
+        E, T = H * HD, S * B
+        nb = (S + 31) // 32
+        share = nb * (nb + 1) / 2 / (nb * nb)
+        qkv, dout = torch.randn(T, 3 * E, device=dev), torch.randn(T, E, device=dev)
+        out, lse, dqkv = torch.empty(T, E, device=dev), torch.empty(B, H, S, device=dev), torch.empty_like(qkv)
+        fwd = lambda: call("rlt_seq_attention_fwd", ptr(qkv), S, B, H, HD, 0.0, 0, ptr(out), ptr(lse), D, stream())
+        bwd = lambda: call("rlt_seq_attention_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, 0.0, 0, ptr(dqkv), None, 0, D, stream())
+        cfwd = lambda: call("rlt_seq_attention_fwd_ex", ptr(qkv), S, B, H, HD, 0.0, 0, N.SEQ_MASK_CAUSAL, ptr(out), ptr(lse), D, stream())
+        cbwd = lambda: call("rlt_seq_attention_bwd_ex", ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, 0.0, 0, N.SEQ_MASK_CAUSAL,
+                            ptr(dqkv), None, 0, D, stream())
+
+
+        def pfwd():
+            assert plib.rlt_seq_attention_fwd(ptr(qkv), S, B, H, HD, 0.0, 0, ptr(out), ptr(lse), D, stream()) == 0
+
+        def pbwd():
+            assert plib.rlt_seq_attention_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), S, B, H, HD, 0.0, 0, ptr(dqkv), None, 0, D, stream()) == 0
+        x = qkv.detach().clone().requires_grad_(True)
+
+        def torch_fwd():
+            q, k, v = x.view(S, B, 3, H, HD).permute(2, 1, 3, 0, 4)
+            o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True)
+            return o.permute(2, 0, 1, 3).reshape(T, E)
+
+        def torch_both():
+            x.grad = None
+            torch_fwd().backward(dout)
+
+        def torch_fwd_only():
+            with torch.no_grad():
+                torch_fwd()
+
+        o_t = torch_fwd().detach()
+        cfwd()
+        torch.cuda.synchronize()
+        tag = f"B{B} S{S} H{H} HD{HD}"
+        print(f"seq_attention_causal {tag}: max |out - torch| = {float((out - o_t).abs().max()):.2e}; expected share of the 32 x 32 "
+              f"products {nb * (nb + 1) // 2} / {nb * nb} = {share:.3f}", flush=True)
+        del o_t
+        for r in range(runs):
+            f, b, cf, cb = (_seq_median_ms(fn, reps) for fn in (fwd, bwd, cfwd, cbwd))
+            tf, tb = _seq_median_ms(torch_fwd_only, reps), _seq_median_ms(torch_both, reps)
+            mine[(tag, r)] = (f, b)
+            print(f"seq_noncausal {tag} run {r} fwd {f:.4f} ms bwd {b:.4f} ms", flush=True)
+            if plib:
+                theirs[(tag, r)] = (_seq_median_ms(pfwd, reps), _seq_median_ms(pbwd, reps))
+                print(f"seq_parent    {tag} run {r} fwd {theirs[(tag, r)][0]:.4f} ms bwd {theirs[(tag, r)][1]:.4f} ms (the parent commit's "
+                      "library, non-causal)", flush=True)
+            print(f"seq_causal    {tag} run {r} fwd {cf:.4f} ms bwd {cb:.4f} ms | causal / non-causal: fwd {cf / f:.3f} bwd {cb / b:.3f} "
+                  f"fwd+bwd {(cf + cb) / (f + b):.3f} (tile count: {share:.3f})"
+                  + ("  (causal is SLOWER than non-causal here)" if cf + cb > f + b else ""), flush=True)
+            print(f"seq_torch     {tag} run {r} sdpa(is_causal) fwd {tf:.4f} ms fwd+bwd {tb:.4f} ms | rlt causal / torch: fwd {cf / tf:.3f} "
+                  f"fwd+bwd {(cf + cb) / tb:.3f}" + ("  (SLOWER than the torch composition here)" if cf + cb > tb or cf > tf else ""), flush=True)
+        del x, qkv, dout, out, lse, dqkv
+        torch.cuda.empty_cache()
+        if layer:
+            from models._common import ParamTree
+            lay = ParamTree(torch.nn.TransformerEncoderLayer(E, H, dropout=0.0)).to(dev)
+            h = torch.randn(T, E, device=dev, requires_grad=True)
+            g = torch.randn(T, E, device=dev)
+            for r in range(runs):
+                ms = {}
+                for causal in (False, True):
+                    def step():
+                        h.grad = None
+                        for p in lay.parameters():
+                            p.grad = None
+                        ops.encoder_layer(h, lay, S, B, H, axis="position", causal=causal).backward(g)
+                    ms[causal] = _seq_median_ms(step, reps)
+                print(f"seq_layer     {tag} run {r} encoder layer step (fwd + bwd), position axis: mask none {ms[False]:.3f} ms, causal "
+                      f"{ms[True]:.3f} ms, causal / none {ms[True] / ms[False]:.3f}", flush=True)
+            del lay, h, g
+            torch.cuda.empty_cache()
+    if not plib:
+        print("seq_parent: RLT_PARENT_LIB not set - no comparison with the parent commit's non-causal kernels", flush=True)
+        return
+    for tag in sorted({t for t, _ in mine}):
+        for i, what in enumerate(("fwd", "bwd")):
+            p, c = [theirs[(tag, r)][i] for r in range(runs)], [mine[(tag, r)][i] for r in range(runs)]
+            spread = max(p) - min(p)
+            diff = sum(c) / len(c) - sum(p) / len(p)
+            print(f"seq_parent    {tag} {what}: parent {p[0]:.4f} / {p[1]:.4f} ms (spread {spread:.4f}), this build non-causal {c[0]:.4f} / {c[1]:.4f} ms, mean difference "
+                  f"{diff:+.4f} ms -> " + ("within the parent's spread" if abs(diff) <= spread else
+                                           ("FASTER than the parent beyond its spread" if diff < 0 else "SLOWER than the parent beyond its spread")),
+                  flush=True)
+
+
 def rerank(shapes=((4096, 300), (1048576, 300)), companions=(1, 3), reps=7, runs=2):
     """rlt_rerank_lists (perm, rank, sorted values and n companion arrays: every output on) against the torch compositions a user
     would otherwise write: torch.sort(-pred, stable=True) + a gather per array (+ a scatter for rank), and argsort +
