@@ -956,6 +956,38 @@ int rlt_heads_bwd(const float* x, const float* w, const int* kinds, int n_heads,
                   float* dx, int accumulate_dx, float* dw, float* db,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ hazard cut head (csrc/hazard.hip)
+ * One Linear(E,1) head whose logit is a STOP logit: a discrete-time hazard parametrisation of the cut distribution, which the
+ * reference does not have (its heads are Linear -> Softmax over all S positions).  0-based positions s = 0..S-1;
+ * x (S*B,E) position-major, w (E), b (1), offset (S) fp32 or NULL - all device memory.
+ *   z_s    = fp32 dot(x_s, w) + b (+ offset_s), accumulated in the order of the softmax heads above
+ *   s < S-1:  stop_s = h_s = sigmoid(z_s),  L_s = - sum_{j<s} softplus(z_j),  p_s = exp(log sigmoid(z_s) + L_s)
+ *   s = S-1:  stop = 1,  p = exp(L_{S-1})  (the remaining mass: "cut at S" cuts nothing); z_{S-1} is written, not used
+ * i.e. p_s = h_s prod_{j<s} (1 - h_j), a distribution over the S cuts; S = 1 gives p = [1], stop = [1].  Everything after the
+ * dot is float64 on the device (softplus, log-sigmoid and exp in their overflow-safe forms) and rounded to fp32 once.
+ * PREFIX GUARANTEE: the sum over j < s runs in position order and is never formed as "total minus suffix", so p[b,s],
+ * stop[b,s] and z[b,s] depend, to the bit, only on rows <= s of list b.  The one exception is p[b,S-1], the remainder.
+ * Deep in a list p underflows to 0, as a softmax head's does; stop does not.
+ *   fwd: p, z (B,S) required, stop (B,S) or NULL; in the reference's (B,S) layout.
+ *   bwd: reads z and nothing else of the forward (a saturated h loses nothing); dp (B,S), dstop (B,S) or NULL.  It recomputes
+ *        h, p, L from z in float64, takes T_j = sum_{k>j} p_k dp_k by a reverse scan in fixed order, and
+ *          j < S-1:  dz_j = (1-h_j) p_j dp_j - h_j T_j + dstop_j h_j (1-h_j);      dz_{S-1} = 0 exactly
+ *        then dx (S*B,E) = dz w (overwritten, or += with accumulate_dx), dw (E) = sum dz x, db (1) = sum dz: per-list partial
+ *        rows in ws, then a fixed-order column reduction.  ws: rlt_hazard_head_bwd_workspace(S,B,E) bytes, 0 for arguments
+ *        out of range.
+ * Limits, those of the heads above: 1 <= S <= 1024, B >= 1, E % 64 == 0, E <= 1024 and at most 4 loads per lane and row (a
+ * lane loads 4 floats where E % 256 == 0, 2 where E % 128 == 0, else 1: E = 64, 128, 192, 256, 384, 512, 768, 1024).  Errors, in this order, before any launch: RLT_E_ARG (a required
+ * pointer NULL, a size not positive), RLT_E_SHAPE (the limits), RLT_E_ALIGN (x, w, dx off 16 bytes), RLT_E_WORKSPACE.
+ * No atomics, no allocation, no host synchronisation; two calls give the same bits.  Algorithmic bytes: fwd reads x once,
+ * 4 S B E, and writes 12 S B; bwd reads x and writes dx once, 8 S B E (12 S B E with accumulate_dx), reads 12 S B and moves
+ * 8 B (E+4) of partial rows: those of a one-head softmax pass over the same shape. */
+int rlt_hazard_head_fwd(const float* x, const float* w, const float* b, const float* offset, int S, int B, int E,
+                        float* p, float* stop, float* z, void* stream);
+size_t rlt_hazard_head_bwd_workspace(int S, int B, int E);
+int rlt_hazard_head_bwd(const float* x, const float* w, const float* z, const float* dp, const float* dstop,
+                        int S, int B, int E, float* dx, int accumulate_dx, float* dw, float* db,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ probe heads (the probing study)
  * models/Classification.py:4-12 (TaskC), models/Rerank.py:4-12 (TaskR), models/Probe.py:30-53,102-122 (TowerClass /
  * TowerRerank as the six probes of Probe), with their training losses of verify_BMT.py:37-44,71-80 and

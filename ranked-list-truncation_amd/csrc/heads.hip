@@ -9,30 +9,11 @@
 // coalesced.  x is read exactly once in forward and once in backward (where dx is written once):
 // HBM-bound, 4*E bytes per token per pass.
 #include "common.h"
+#include "row_vec.h"
 
 namespace {
 
 constexpr int MAXH = 3, MAXCH = 4, MAXS = 1024;
-
-template <int V> struct VecT;
-template <> struct VecT<1> { typedef float T; };
-template <> struct VecT<2> { typedef float2 T; };
-template <> struct VecT<4> { typedef float4 T; };
-template <int V>
-__device__ __forceinline__ void ldv(const float* p, float (&d)[V]) {
-    typename VecT<V>::T v = *reinterpret_cast<const typename VecT<V>::T*>(p);
-    const float* f = reinterpret_cast<const float*>(&v);
-#pragma unroll
-    for (int i = 0; i < V; ++i) d[i] = f[i];
-}
-template <int V>
-__device__ __forceinline__ void stv(float* p, const float (&d)[V]) {
-    typename VecT<V>::T v;
-    float* f = reinterpret_cast<float*>(&v);
-#pragma unroll
-    for (int i = 0; i < V; ++i) f[i] = d[i];
-    *reinterpret_cast<typename VecT<V>::T*>(p) = v;
-}
 
 struct HeadKinds { int k[MAXH]; };
 
@@ -207,7 +188,6 @@ __global__ __launch_bounds__(256) void choopy_embed_kernel(const float* __restri
 }
 
 int ew_grid(size_t n) { size_t g = (n + 1023) / 1024; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
-int pick_v(int E) { return (E % 256 == 0) ? 4 : ((E % 128 == 0) ? 2 : 1); }
 
 }  // namespace
 

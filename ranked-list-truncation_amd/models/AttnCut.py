@@ -1,7 +1,6 @@
 """AttnCut on the HIP hot path - drop-in for the reference's models/AttnCut.py:5-20."""
 from torch import nn
 
-from rlt_hip import native as N
 from rlt_hip import ops
 from . import _common as C
 
@@ -11,10 +10,12 @@ class AttnCut(C.CutModel):
     positions.  Same constructor, state_dict keys and output shape (B,S,1) as the reference."""
 
     def __init__(self, input_size: int = 3, d_model: int = 256, n_head: int = 4, num_layers: int = 1,
-                 dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none"):
+                 dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none",
+                 cut_head: str = "softmax", hazard_prior: str = "uniform"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
         self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
+        self.cut_head, self.hazard_prior = C.check_cut_head(cut_head, hazard_prior)
         self.n_head, self.dropout = n_head, dropout
         self.encoding_layer = C.bilstm_params(input_size)
         self.attention_layer = C.encoder_params(d_model, n_head, num_layers, dropout)
@@ -26,5 +27,4 @@ class AttnCut(C.CutModel):
         B, S, _ = x.shape
         h = C.bilstm(ops.to_position_major(x), self.encoding_layer, S, B)
         h = C.encoder(h, self.attention_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal")
-        head = getattr(self.decison_layer, "0")
-        return ops.heads(h, [head.weight], [head.bias], [N.HEAD_SOFTMAX], S, B)[0]
+        return C.cut_head(self, h, S, B)

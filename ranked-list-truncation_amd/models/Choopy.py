@@ -2,17 +2,18 @@
 import torch
 from torch import nn
 
-from rlt_hip import native as N
 from rlt_hip import ops
 from . import _common as C
 
 
 class Choopy(C.CutModel):
     def __init__(self, seq_len: int = 300, d_model: int = 128, n_head: int = 8, num_layers: int = 3, dropout=0.2,
-                 attention_axis: str = "list", attention_mask: str = "none"):
+                 attention_axis: str = "list", attention_mask: str = "none",
+                 cut_head: str = "softmax", hazard_prior: str = "uniform"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
         self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
+        self.cut_head, self.hazard_prior = C.check_cut_head(cut_head, hazard_prior)
         self.seq_len, self.n_head, self.dropout = seq_len, n_head, dropout
         self.position_encoding = nn.Parameter(torch.randn(seq_len, 127), requires_grad=True)
         self.attention_layer = C.encoder_params(d_model, n_head, num_layers, dropout)
@@ -26,5 +27,4 @@ class Choopy(C.CutModel):
             raise ValueError(f"Choopy was built for seq_len={self.seq_len}, got {S}")
         h = ops.choopy_embed(x, self.position_encoding)
         h = C.encoder(h, self.attention_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal")
-        head = getattr(self.decison_layer, "0")
-        return ops.heads(h, [head.weight], [head.bias], [N.HEAD_SOFTMAX], S, B)[0]
+        return C.cut_head(self, h, S, B)

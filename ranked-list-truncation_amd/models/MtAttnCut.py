@@ -8,10 +8,12 @@ from ._mt import mt_heads
 
 class MtAttnCut(C.CutModel):
     def __init__(self, input_size: int = 3, d_model: int = 256, n_head: int = 4, num_layers: int = 1,
-                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none"):
+                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none",
+                 cut_head: str = "softmax", hazard_prior: str = "uniform"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
         self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
+        self.cut_head, self.hazard_prior = C.check_cut_head(cut_head, hazard_prior)
         self.num_tasks, self.n_head, self.dropout = num_tasks, n_head, dropout
         self.pre_encoding = C.bilstm_params(input_size)
         self.encoding_layer = C.encoder_params(d_model, n_head, num_layers, dropout)

@@ -9,10 +9,12 @@ from ._mt import mt_heads
 
 class MtChoopy(C.CutModel):
     def __init__(self, seq_len: int = 300, d_model: int = 128, n_head: int = 8, num_layers: int = 3,
-                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none"):
+                 num_tasks: float = 3, dropout: float = 0.4, attention_axis: str = "list", attention_mask: str = "none",
+                 cut_head: str = "softmax", hazard_prior: str = "uniform"):
         super().__init__()
         self.attention_axis = C.check_attention_axis(attention_axis)
         self.attention_mask = C.check_attention_mask(attention_mask, attention_axis)
+        self.cut_head, self.hazard_prior = C.check_cut_head(cut_head, hazard_prior)
         self.seq_len, self.num_tasks, self.n_head, self.dropout = seq_len, num_tasks, n_head, dropout
         self.position_encoding = nn.Parameter(torch.randn(seq_len, 127), requires_grad=True)
         self.encoding_layer = C.encoder_params(d_model, n_head, num_layers, dropout)

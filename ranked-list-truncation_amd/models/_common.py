@@ -81,6 +81,33 @@ def check_attention_mask(mask, axis):
     return mask
 
 
+CUT_HEADS = ("softmax", "hazard")
+HAZARD_PRIORS = ("uniform", "none")
+
+
+def check_cut_head(cut_head, hazard_prior="uniform"):
+    """'softmax' (Linear -> softmax over the S positions: the reference's head, the default) or 'hazard' (the logit is a stop
+    logit, p_s = h_s prod_{j<s} (1 - h_j): ops.hazard_head, whose value at rank s reads ranks <= s only); hazard_prior 'uniform'
+    (the fixed offset under which zero weights give the uniform cut distribution) or 'none'.  Anything else is a ValueError.
+    Neither changes a parameter: state_dicts load across heads.  -> (cut_head, hazard_prior)"""
+    if cut_head not in CUT_HEADS:
+        raise ValueError(f"cut_head must be one of {CUT_HEADS}, got {cut_head!r}")
+    if hazard_prior not in HAZARD_PRIORS:
+        raise ValueError(f"hazard_prior must be one of {HAZARD_PRIORS}, got {hazard_prior!r}")
+    return cut_head, hazard_prior
+
+
+def cut_head(module, h, S, B):
+    """The cut distribution (B,S,1) of `module` (a CutModel with a `decison_layer`) from the encoder output h (S*B,E)."""
+    lin = getattr(module.decison_layer, "0")
+    if module.cut_head == "softmax":
+        return ops.heads(h, [lin.weight], [lin.bias], [N.HEAD_SOFTMAX], S, B)[0]
+    p, stop = ops.hazard_head(h, lin.weight, lin.bias, S, B, module.hazard_offset(S, h.device))
+    if module._stop_sink is not None:
+        module._stop_sink.append(stop)
+    return p.unsqueeze(2)
+
+
 def encoder(x_pm, params, n_head, S, B, drop_p=0.0, axis="list", causal=False):
     """Stack of post-norm encoder layers with list-axis (axis='list') or within-list (axis='position') attention.  drop_p > 0
     applies the four dropouts of nn.TransformerEncoderLayer: attention probabilities, dropout1 (attention branch),
@@ -123,28 +150,61 @@ class _CallableHead:
 class CutModel(nn.Module):
     """Common base of the truncation models: `truncate` says where the model cuts each list, with no labels."""
 
+    cut_head, hazard_prior = "softmax", "uniform"      # the models that take `cut_head=` set their own
+    _stop_sink = None                                   # a list while stop_probabilities runs the forward
+
+    def hazard_offset(self, S, device):
+        """The hazard head's fixed prior offset for lists of S positions on `device` (ops.hazard_prior_offset), None under
+        hazard_prior='none'.  Not a parameter and not in the state_dict: built once per (S, device) and kept."""
+        if self.hazard_prior == "none":
+            return None
+        cache = self.__dict__.setdefault("_hazard_offsets", {})
+        key = (int(S), str(device))
+        if key not in cache:
+            cache[key] = ops.hazard_prior_offset(S, device)
+        return cache[key]
+
+    def _eval_outputs(self, x):
+        """forward(x) in eval mode under no_grad -> (the cut head's output, the stop probabilities (B,S) or None); the module's
+        train / eval state is restored."""
+        was_training = self.training
+        self.eval()
+        self._stop_sink = sink = []
+        try:
+            with torch.no_grad():
+                out = self(x)
+        finally:
+            self._stop_sink = None
+            self.train(was_training)
+        return (out[-1] if isinstance(out, (list, tuple)) else out), (sink[-1] if sink else None)
+
+    def stop_probabilities(self, x):
+        """x: what forward takes.  Runs a cut_head='hazard' model in eval mode under no_grad and returns its stop probabilities
+        (B,S): stop[b,s] = P(cut at s+1 | no cut before), 1 at the last position - what truncate(rule='above') sweeps.  Row s
+        is computed from what the encoder gives for ranks <= s.  A softmax-head model has none: ValueError."""
+        if self.cut_head != "hazard":
+            raise ValueError(f"{type(self).__name__} with cut_head={self.cut_head!r} has no stop probabilities: build it with cut_head='hazard'")
+        return self._eval_outputs(x)[1]
+
     def truncate(self, x, *, rule=None, tau=None):
         """x: what forward takes (BiCut with sparse_input: an ops.SparseBatch).  Runs the model in eval mode under no_grad and
         returns (k (B,) int32, p_k (B,) float32) on the device: each list's cut and the winning value (rlt_cut_report, label-free:
         first maximum + 1, or BiCut's rule on its (B,S,2) output).  The module's train / eval state is restored.
         With `rule` and `tau` set ('quantile' | 'above' | 'score' and one threshold: ops.cut_sweep) the model's output is cut by
         that rule instead - BiCut's class-0 column at stride 2 - and only k (B,) int32 is returned (rlt_cut_sweep, label-free,
-        T = 1; k may be 0 under 'score')."""
+        T = 1; k may be 0 under 'score').  A cut_head='hazard' model is swept on its stop probabilities under 'above' (the
+        first rank whose stop probability reaches tau: a decision made at that rank); every other rule reads p."""
         if (rule is None) != (tau is None):
             raise ValueError("truncate: pass both `rule` and `tau`, or neither")
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                out = self(x)
-                cut = out[-1] if isinstance(out, (list, tuple)) else out
-                if rule is not None:
-                    thr = torch.full((1,), float(tau), dtype=torch.float64, device=cut.device)
-                    k, _ = ops.cut_sweep(cut, thr, rule)
-                    return k.reshape(-1)
-                per, _ = ops.cut_report(cut)
-        finally:
-            self.train(was_training)
+        cut, stop = self._eval_outputs(x)
+        with torch.no_grad():
+            if rule is not None:
+                if rule == "above" and stop is not None:
+                    cut = stop
+                thr = torch.full((1,), float(tau), dtype=torch.float64, device=cut.device)
+                k, _ = ops.cut_sweep(cut, thr, rule)
+                return k.reshape(-1)
+            per, _ = ops.cut_report(cut)
         return per["k"], per["p_k"]
 
     _TOWER_HEADS = {"TowerClass": "classi", "TowerRerank": "rerank", "TowerCut": "decison_layer"}

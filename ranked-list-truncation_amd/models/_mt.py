@@ -8,6 +8,8 @@ _KIND = {"classi": N.HEAD_SIGMOID, "rerank": N.HEAD_IDENTITY, "decison_layer": N
 
 def mt_heads(module, h, S, B):
     names = C.pick_tasks(module.num_tasks)
+    if module.cut_head == "hazard":
+        names = names[:-1]              # the cut head, always last, goes through the hazard pass; the others as they do
     ws, bs, kinds = [], [], []
     for name in names:
         holder = getattr(module, name)
@@ -15,4 +17,7 @@ def mt_heads(module, h, S, B):
         ws.append(lin.weight)
         bs.append(lin.bias)
         kinds.append(_KIND[name])
-    return ops.heads(h, ws, bs, kinds, S, B)
+    outs = ops.heads(h, ws, bs, kinds, S, B)
+    if module.cut_head == "hazard":
+        outs.append(C.cut_head(module, h, S, B))
+    return outs

@@ -127,6 +127,10 @@ _SIGNATURES = {
     "rlt_heads_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "rlt_heads_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "rlt_heads_bwd": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
+    # hazard cut head: stop probabilities and the cut distribution they imply (csrc/hazard.hip)
+    "rlt_hazard_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "rlt_hazard_head_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "rlt_hazard_head_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
     "rlt_mmoe_gate_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rlt_mmoe_gate_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rlt_mmoe_gate_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_size_t, P]),

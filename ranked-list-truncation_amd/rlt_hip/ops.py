@@ -914,6 +914,59 @@ def heads(x, weights, biases, kinds, S, B):
     return [out[i].unsqueeze(2) for i in range(len(kinds))]          # each (B,S,1)
 
 
+class HazardHeadFn(Function):
+    """Linear(E,1) stop logits -> (p, stop), both (B,S): stop_s = sigmoid(z_s), p_s = stop_s prod_{j<s} (1 - stop_j), the last
+    position taking the remaining mass (rlt_hazard_head_fwd).  The tape keeps z: the backward recomputes the rest from it."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, offset, S, B):
+        E = w.numel()
+        p, stop, z = _empty((B, S), x), _empty((B, S), x), _empty((B, S), x)
+        call("rlt_hazard_head_fwd", ptr(x), ptr(w), ptr(b), ptr(offset), S, B, E, ptr(p), ptr(stop), ptr(z), stream())
+        ctx.meta = (S, B)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, w, z)
+        return p, stop
+
+    @staticmethod
+    def backward(ctx, dp, dstop):
+        x, w, z = ctx.saved_tensors
+        S, B = ctx.meta
+        E = w.numel()
+        # an output nothing read has no gradient (None): the losses read p alone, and dstop = NULL is the kernel's own form of that
+        dp = torch.zeros_like(z) if dp is None else N.f32c(dp)
+        dstop = None if dstop is None else N.f32c(dstop)
+        dx = _empty((S * B, E), x)
+        dw, db = _empty((1, E), x), _empty((1,), x)
+        ws_bytes = query("rlt_hazard_head_bwd_workspace", S, B, E)
+        ws = workspace(ws_bytes, x.device)
+        call("rlt_hazard_head_bwd", ptr(x), ptr(w), ptr(z), ptr(dp), ptr(dstop), S, B, E, ptr(dx), 0, ptr(dw), ptr(db),
+             ptr(ws), ws_bytes, stream())
+        return dx, dw, db, None, None, None
+
+
+def hazard_prior_offset(S, device=None):
+    """(S,) fp32: offset_s = -log(S-1-s) for s < S-1, 0 at the end.  With it a zero weight and bias give the uniform cut
+    distribution (stop_s = 1 / (S-s)); without it they give a geometric one with mean 2."""
+    off = torch.zeros(S, dtype=torch.float32)
+    if S > 1:
+        off[:S - 1] = -torch.log(torch.arange(S - 1, 0, -1, dtype=torch.float64)).float()
+    return off if device is None else off.to(device)
+
+
+def hazard_head(x_pm, weight, bias, S, B, offset=None):
+    """x_pm (S*B,E) position-major, weight (1,E) or (E,), bias (1,), offset (S,) or None -> (p, stop), each (B,S) and
+    differentiable.  p[b,s], stop[b,s] depend, to the bit, on rows <= s of list b only (p[b,S-1] excepted)."""
+    E = x_pm.shape[1]
+    if weight.numel() != E or bias.numel() != 1:
+        raise ValueError(f"hazard_head: one weight row of {E} and one bias, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    if offset is not None:
+        if offset.numel() != S:
+            raise ValueError(f"hazard_head: offset must have S = {S} elements, got {tuple(offset.shape)}")
+        offset = N.f32c(offset.detach())
+    return HazardHeadFn.apply(N.f32c(x_pm), N.f32c(weight.reshape(1, E)), N.f32c(bias.reshape(1)), offset, S, B)
+
+
 # ------------------------------------------------------------------------------ MMOE
 class MMOEGateFn(Function):
     """gates (n_tasks,B,n_e) = softmax_e(flatten_s(h[b]) @ w_gate[t])."""

@@ -94,6 +94,8 @@ class ScalarLog:
 class Trainer:
     attention_axis = "list"      # of a trainer a driver assembles by hand (verify_probe.py); __init__ sets the run's
     attention_mask = "none"      # likewise
+    cut_head = "softmax"         # likewise
+    hazard_prior = "uniform"     # likewise
     rerank_by = None             # --rerank-eval, likewise
 
     def __init__(self, args):
@@ -160,6 +162,18 @@ class Trainer:
         # the axis, but only when it is 'causal': the files of a default run are byte for byte what they were
         self.attention_mask = mask = getattr(args, "attention_mask", "none")
         mask_kw = {"attention_mask": mask} if mask != "none" else {}
+        # --cut-head: 'softmax' (the reference's head), or 'hazard' (stop probabilities, ops.hazard_head) on the four models that
+        # take it.  It changes no parameter; recorded like the mask, only when it is not the default
+        self.cut_head = getattr(args, "cut_head", "softmax")
+        self.hazard_prior = getattr(args, "hazard_prior", "uniform")
+        if self.cut_head != "softmax":
+            if name not in ('choopy', 'attncut', 'mtchoopy', 'mtattncut'):
+                raise ValueError(f"--cut-head {self.cut_head}: {name} has the softmax cut head only (choopy, attncut, mtchoopy and "
+                                 "mtattncut take a hazard head)")
+            mask_kw.update(cut_head=self.cut_head, hazard_prior=self.hazard_prior)
+            if (axis, mask) != ("position", "causal"):
+                logging.warning('--cut-head hazard without --attention-axis position --attention-mask causal: the head reads ranks '
+                                '<= i at rank i, but the encoder under it does not, so the stop probabilities are not online')
         # --rerank-loss: the loss of the rerank head inside MtCutLoss - the reference's batch-wide hinge, or a pairwise RankNet /
         # LambdaRank loss (utils.losses.PairwiseRankLoss); the default builds the criterion exactly as before
         rr_loss = getattr(args, "rerank_loss", "hinge")
@@ -396,8 +410,12 @@ class Trainer:
                 path, stored_mask, self.attention_mask))
 
     def _mask_record(self):
-        """{'attention_mask': 'causal'} for a causal run, {} otherwise: a default run writes no new key"""
-        return {"attention_mask": self.attention_mask} if self.attention_mask != "none" else {}
+        """{'attention_mask': 'causal'} for a causal run, {'cut_head': 'hazard', 'hazard_prior': ...} for a hazard-head run, {}
+        otherwise: a default run writes no new key"""
+        rec = {"attention_mask": self.attention_mask} if self.attention_mask != "none" else {}
+        if self.cut_head != "softmax":
+            rec.update(cut_head=self.cut_head, hazard_prior=self.hazard_prior)
+        return rec
 
     def save_model(self):
         os.makedirs(self.save_path, exist_ok=True)
@@ -515,6 +533,10 @@ class Trainer:
             out = self.model(x)
         return out[-1] if isinstance(out, (list, tuple)) else out
 
+    def _forward_eval_stop(self, x):
+        """(the cut distribution, the stop probabilities (B,S)) of one batch of a hazard-head model, eval mode, no gradient."""
+        return self.model._eval_outputs(x.to(self.device, non_blocking=True))
+
     def report(self, path, split="test", labelled=True):
         """--report-out: every list of `split`, length bucket by length bucket, through the model and `CutReport`; one .npz with
         the per-query arrays (rows in the order of `qid`), and per list length the k histogram, the two curves and the summary
@@ -560,6 +582,9 @@ class Trainer:
         per_len["attention_axis"] = np.asarray(self.attention_axis)
         if self.attention_mask != "none":
             per_len["attention_mask"] = np.asarray(self.attention_mask)
+        if self.cut_head != "softmax":
+            per_len["cut_head"] = np.asarray(self.cut_head)
+            per_len["hazard_prior"] = np.asarray(self.hazard_prior)
         if self.rerank_by and labelled:
             per_len["rerank_by"] = np.asarray(self.rerank_by)
         np.savez(path, qid=np.asarray(qid_all), length=np.asarray(len_all, dtype=np.int32), lengths=np.asarray(sorted(map(int, summaries))),
@@ -608,8 +633,13 @@ class Trainer:
                 sw = CutSweep(L, rule, th, device=self.device, reward=reward)
                 for i in range(0, x.shape[0], self.batch_size):
                     xb, yb = x[i:i + self.batch_size], y[i:i + self.batch_size]
-                    v = xb[..., 0].to(self.device, non_blocking=True) if rule == "score" else self._forward_eval(xb)
-                    sw.update(v, yb)
+                    if rule == "above" and self.cut_head == "hazard":
+                        # the rule's own input: the first rank whose STOP probability reaches tau (the argmax report keeps p)
+                        v, stop = self._forward_eval_stop(xb)
+                        sw.update(stop, yb)
+                    else:
+                        v = xb[..., 0].to(self.device, non_blocking=True) if rule == "score" else self._forward_eval(xb)
+                        sw.update(v, yb)
                     if argmax is not None and split == "test":
                         argmax.update(v, yb)
                 sweeps[split] = sw
@@ -796,6 +826,15 @@ def build_parser():
                    help="'causal' (needs --attention-axis position): position i attends to the positions <= i of its list, so the "
                         "encoder's output at rank i does not look below rank i (Choopy's logits are then prefix-only; AttnCut's "
                         "BiLSTM and every softmax over positions stay global).  Recorded beside the axis when it is 'causal'")
+    p.add_argument('--cut-head', type=str, default='softmax', choices=('softmax', 'hazard'),
+                   help="'hazard' (choopy, attncut, mtchoopy, mtattncut): the cut head emits a stop probability per position and "
+                        "the cut distribution is p_s = h_s prod_{j<s} (1 - h_j), the last position taking the rest; its value at "
+                        "rank i reads ranks <= i only, so with --attention-axis position --attention-mask causal Choopy's stop "
+                        "probabilities are online and --cut-sweep above:... sweeps them.  Same parameters: checkpoints load across "
+                        "heads.  Recorded in checkpoints and reports when it is 'hazard'")
+    p.add_argument('--hazard-prior', type=str, default='uniform', choices=('uniform', 'none'),
+                   help="fixed offset of the hazard head's logits: 'uniform' = -log(S-1-s), under which zero weights give the uniform "
+                        "cut distribution (without it they give a geometric one with mean 2, which cannot reach long cuts)")
     p.add_argument('--history-json', type=str, default=None, help="rank 0 writes the per-epoch train / test means and the best / best-5 figures here")
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "

@@ -1584,6 +1584,71 @@ def pair_rank(shapes=((4096, 300), (1048576, 40)), reps=7, runs=2):
                     torch.cuda.empty_cache()
 
 
+def hazard(shapes=((4096, 300, 256), (8192, 300, 128)), reps=7, runs=2):
+    """rlt_hazard_head_fwd / _bwd at (B, S, E) against their yardstick - rlt_heads_fwd / _bwd with ONE softmax head at the same
+    shape, in the same job: both passes read x once (forward) or read x and write dx once (backward), equal algorithmic bytes -
+    and against a torch composition of the same head (linear, logsigmoid, cumsum, exp, autograd).  The median of `reps` HIP-event
+    timings in each of `runs` separate runs; GB/s on the algorithmic bytes 4 S B E (forward) and 8 S B E (backward)."""
+    for B, S, E in shapes:
+        g = torch.Generator(device=dev).manual_seed(7)
+        x = torch.randn(S * B, E, device=dev, generator=g)
+        w = torch.randn(1, E, device=dev, generator=g) / E ** 0.5
+        b = torch.randn(1, device=dev, generator=g)
+        off = ops.hazard_prior_offset(S, dev)
+        dp, dstop = torch.randn(B, S, device=dev, generator=g), torch.randn(B, S, device=dev, generator=g)
+        p, stop, z, out = (torch.empty(B, S, device=dev) for _ in range(4))
+        dx, dw, db = torch.empty(S * B, E, device=dev), torch.empty(1, E, device=dev), torch.empty(1, device=dev)
+        kinds = (N.c_int * 1)(N.HEAD_SOFTMAX)
+        hz_bytes = N.query("rlt_hazard_head_bwd_workspace", S, B, E)
+        hd_bytes = N.query("rlt_heads_bwd_workspace", 1, S, B, E)
+        hz_ws, hd_ws = N.workspace(hz_bytes, dev), N.workspace(hd_bytes, dev)
+
+        def hz_fwd():
+            call("rlt_hazard_head_fwd", ptr(x), ptr(w), ptr(b), ptr(off), S, B, E, ptr(p), ptr(stop), ptr(z), stream())
+
+        def hz_bwd():
+            call("rlt_hazard_head_bwd", ptr(x), ptr(w), ptr(z), ptr(dp), ptr(dstop), S, B, E, ptr(dx), 0, ptr(dw), ptr(db),
+                 ptr(hz_ws), hz_bytes, stream())
+
+        def hd_fwd():
+            call("rlt_heads_fwd", ptr(x), ptr(w), ptr(b), kinds, 1, S, B, E, ptr(out), stream())
+
+        def hd_bwd():
+            call("rlt_heads_bwd", ptr(x), ptr(w), kinds, 1, ptr(out), ptr(dp), S, B, E, ptr(dx), 0, ptr(dw), ptr(db),
+                 ptr(hd_ws), hd_bytes, stream())
+
+        F = torch.nn.functional
+        xt, wt, bt = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+
+        def composed(backward):
+            zz = (F.linear(xt, wt, bt).view(S, B).t() + off)[:, :S - 1]
+            L = torch.cat([zz.new_zeros(B, 1), torch.cumsum(F.logsigmoid(-zz), 1)], 1)
+            pp = torch.exp(torch.cat([F.logsigmoid(zz), zz.new_zeros(B, 1)], 1) + L)
+            ss = torch.cat([torch.sigmoid(zz), zz.new_ones(B, 1)], 1)
+            if backward:
+                xt.grad = wt.grad = bt.grad = None
+                torch.autograd.backward([pp, ss], [dp, dstop])
+            return pp
+
+        hz_fwd()
+        err = float((p - composed(False).detach()).abs().max())
+        for r in range(runs):
+            med = {"rlt_hazard_head_fwd": _seq_median_ms(hz_fwd, reps), "rlt_heads_fwd (1 softmax head)": _seq_median_ms(hd_fwd, reps),
+                   "torch composition fwd": _seq_median_ms(lambda: composed(False), reps),
+                   "rlt_hazard_head_bwd": _seq_median_ms(hz_bwd, reps), "rlt_heads_bwd (1 softmax head)": _seq_median_ms(hd_bwd, reps),
+                   "torch composition fwd+bwd": _seq_median_ms(lambda: composed(True), reps)}
+            for name, ms in med.items():
+                nbytes = (8 if "bwd" in name else 4) * S * B * E
+                print(f"hazard B{B} S{S} E{E} run {r} {name:32s}: {ms * 1e3:9.1f} us  {nbytes / ms / 1e6:8.1f} GB/s", flush=True)
+            print(f"hazard B{B} S{S} E{E} run {r} hazard / heads: fwd {med['rlt_hazard_head_fwd'] / med['rlt_heads_fwd (1 softmax head)']:.3f}x, "
+                  f"bwd {med['rlt_hazard_head_bwd'] / med['rlt_heads_bwd (1 softmax head)']:.3f}x; torch / hazard: fwd "
+                  f"{med['torch composition fwd'] / med['rlt_hazard_head_fwd']:.1f}x, fwd+bwd "
+                  f"{med['torch composition fwd+bwd'] / (med['rlt_hazard_head_fwd'] + med['rlt_hazard_head_bwd']):.1f}x; "
+                  f"max |p - torch fp32| = {err:.1e}", flush=True)
+        del x, dx, xt
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
