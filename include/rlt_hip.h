@@ -756,6 +756,37 @@ int rlt_seq_attention_bwd_ex(const float* qkv, const float* out, const float* do
                              int S, int B, int H, int HD, float drop_p, uint32_t seed, int mask, float* dqkv,
                              void* ws, size_t ws_bytes, int precision, void* stream);
 
+/* ------------------------------------------------------------------ streaming: K/V-cached append attention
+ * The causal within-list forward, one CHUNK of ranks at a time (csrc/attention_seq_append.hip; inference only: no dropout, no
+ * backward).  tests: tests/test_stream_abi.py, tests/test_seq_append_gpu.py.
+ *   qkv_chunk: (C*B, 3E) position-major, row i*B + b = [q | k | v] of rank t0 + i of list b - the in_proj of the chunk's rows.
+ *   kv_cache:  (Smax*B, 2E) position-major, row s*B + b = [K | V] of rank s of list b.  The CALLER owns it: 8*Smax*B*E bytes,
+ *              one per encoder layer, alive from the list's first chunk to its last.  It need not be initialised: the call reads
+ *              rows < t0 only (what earlier calls appended) and writes rows t0 .. t0+C-1; rows >= t0+C are neither read nor
+ *              written.
+ *   active:    (B) int32 or NULL; active[b] == 0 retires list b: its workgroups leave at once, and its rows of out, of lse and of
+ *              the cache are UNTOUCHED (not zeroed).  NULL: every list is active.
+ *   out: (C*B, E), row i*B + b.  lse: (B,H,C) or NULL.
+ * For an active list the call appends the chunk's K | V columns to cache rows t0 .. t0+C-1 and writes the attention of the C new
+ * queries over ranks 0 .. t0+i.  PREFIX STATEMENT: out and lse of rank t0+i are, as fp32 values, those that
+ * rlt_seq_attention_fwd_ex with RLT_SEQ_MASK_CAUSAL and drop_p = 0 gives for that rank on the whole list - whatever the chunking,
+ * zero tolerance.  The kernel has the one-shot kernel's geometry and device functions (csrc/attention_seq_tile.h): passes aligned to
+ * absolute multiples of 32 ranks, row q over the 32-key sub-tiles 0 .. floor(q/32) in order, keys > q at weight 0.  The tile
+ * rows >= t0+C are staged as zeros where the one-shot call stages ranks behind the query (weight 0 either way): the sign of an
+ * exactly-zero sum is the one thing that may differ (+0 against -0).  After the last chunk the cache holds the K | V columns of
+ * the list's qkv bit for bit.  A tile is staged from the cache (ranks < t0) and from the chunk itself (ranks >= t0): the kernel
+ * never reads a cache row it writes in the same launch.
+ * Limits and errors are those of rlt_seq_attention_fwd_ex with Smax for S, before any launch and in this order: RLT_E_ARG (a bad
+ * precision code; qkv_chunk, kv_cache or out NULL; C, Smax, B or H not positive; t0 < 0; t0 + C > Smax), RLT_E_SHAPE (HD not 16
+ * or 64, Smax > 1024, the index limits), RLT_E_ALIGN (qkv_chunk, kv_cache, out or lse off 16 bytes).  The three precision codes
+ * run the same exact-fp32 kernel.  No allocation, no host synchronisation, no atomics; two calls give the same bits.  Calls on one
+ * cache must be ordered (one stream, or events): chunk t0 reads what the chunks before it wrote.
+ * Algorithmic bytes per active list: reads 12*C*E (the chunk) + 8*t0*E (the cache), writes 8*C*E (cache) + 4*C*E + 4*H*C.  At
+ * C = 1 one of a wavefront's 32 query lanes works and the call is bound by the 8*t0*B*E cache read; the key range is NOT split
+ * across wavefronts, which would change the order of the sums and give up the prefix statement. */
+int rlt_seq_attention_append(const float* qkv_chunk, float* kv_cache, int t0, int C, int Smax, int B, int H, int HD,
+                             const int32_t* active, float* out, float* lse, int precision, void* stream);
+
 /* ------------------------------------------------------------------ BiLSTM recurrence (M2)
  * One bidirectional LSTM layer with hidden size 128 (nn.LSTM(..., hidden_size=128,
  * bidirectional=True, batch_first=True), models/AttnCut.py:8): gate order i,f,g,o, h0=c0=0.
@@ -987,6 +1018,31 @@ size_t rlt_hazard_head_bwd_workspace(int S, int B, int E);
 int rlt_hazard_head_bwd(const float* x, const float* w, const float* z, const float* dp, const float* dstop,
                         int S, int B, int E, float* dx, int accumulate_dx, float* dw, float* db,
                         void* ws, size_t ws_bytes, void* stream);
+/* streaming: the hazard head one CHUNK of positions t0 .. t0+C-1 at a time, with the stop decision taken on the device
+ * (csrc/hazard.hip; tests/test_stream_abi.py, tests/test_hazard_append_gpu.py).  Inference only.
+ *   x (C*B,E) position-major: the encoder output of the chunk, row i*B + b = position t0+i of list b.  offset (C) or NULL: the
+ *   chunk's slice offset[t0 .. t0+C-1] of the list's prior offset.  carry (B) float64, in and out: L = - sum_{j<t0} softplus(z_j)
+ *   of each list - the caller ZEROES it before the chunk at t0 = 0 and hands it on unchanged from call to call.
+ *   stop (B,C) required; p, z (B,C) or NULL.  final != 0: the chunk ends the list; only then does its last row take stop = 1 and
+ *   p = the remaining mass.  Without it every row is an inner row (stop = sigmoid(z), p = exp(log sigmoid(z) + L)).
+ *   The dot, the float64 terms and the rounding are those of rlt_hazard_head_fwd (one device text), the prefix sum starts from
+ *   carry and continues in position order.  PREFIX STATEMENT: stop and z of position t0+i are, to the bit, those of the one-shot
+ *   call on the whole list, whatever the chunking (the last position under final included).  p is the fp32 rounding of a float64
+ *   whose prefix sum is associated per chunk: it differs from the one-shot float64 by rounding errors of that sum (about 1e-16
+ *   relative to L), so its fp32 rounding is the one-shot p except where such a difference straddles an fp32 rounding boundary; one
+ *   chunk of the whole list is the one-shot computation itself.  carry after the last chunk is - sum_j softplus(z_j).
+ *   DECISION: active (B) int32 in and out, or NULL (then no decision is taken and k is not read).  For a list with
+ *   active[b] != 0, the first row i of the chunk with (double)stop[b,i] >= tau - the comparison of rlt_cut_sweep's
+ *   RLT_SWEEP_FIRST_ABOVE (a NaN compares false) - sets k[b] = t0 + i + 1 and active[b] = 0; under final a list that no row stopped
+ *   stops at the last row, k[b] = t0 + C.  The chunk's rows behind the stop are still written (the list retires for the NEXT call).
+ *   A list with active[b] == 0 on entry is skipped: its carry, k, stop, p and z are UNTOUCHED.
+ * Limits and errors, those of the hazard head with C for S, before any launch and in this order: RLT_E_ARG (x, w, b, carry or stop
+ * NULL, active without k, C / B / E not positive, t0 < 0), RLT_E_SHAPE, RLT_E_ALIGN (x, w off 16 bytes).  No atomics, no
+ * allocation, no host synchronisation; two calls from the same carry / active / k give the same bits.  One stream: a chunk reads
+ * what the chunk before it left in carry and active.  Algorithmic bytes per active list: reads 4*C*E, writes up to 12*C + 16. */
+int rlt_hazard_head_append(const float* x, const float* w, const float* b, const float* offset, int t0, int C, int B, int E,
+                           int final, double* carry, double tau, int32_t* active, int32_t* k, float* stop, float* p, float* z,
+                           void* stream);
 
 /* ------------------------------------------------------------------ probe heads (the probing study)
  * models/Classification.py:4-12 (TaskC), models/Rerank.py:4-12 (TaskR), models/Probe.py:30-53,102-122 (TowerClass /

@@ -6,6 +6,8 @@
 // over the four wavefronts, the prefix sum of the softplus terms is taken by wavefront 0 in position order (wave_scan_op over
 // rounds of 64 lanes plus a carried scalar) - never as "total minus suffix", so p, stop and z at position s are functions, to
 // the bit, of the rows <= s of the list (p at S-1 excepted: it is the remainder).  x is read once per pass, dx written once.
+// hazard_append_kernel (rlt_hazard_head_append) is the forward on a chunk of positions, from the same device functions: the prefix
+// starts from a carried sum, the last row is the remainder only when the chunk ends the list, and the stop decision is taken here.
 #include "common.h"
 #include "row_vec.h"
 
@@ -26,9 +28,9 @@ __device__ __forceinline__ HzTerms hz_terms(double z) {
 }
 
 // wavefront 0: logp[s] -= sum_{j<s} a[j] for s < S, in position order (lane s of a round adds a[s-1]; the carry is the sum of
-// the rounds before).  What position s receives is computed from a[0..s-1] alone.
-__device__ __forceinline__ void hz_prefix(const double* a, double* logp, int S, int lane) {
-    double carry = 0.0;
+// the rounds before).  What position s receives is computed from a[0..s-1] alone - and from `carry`, the sum the caller brings
+// along (hazard_append_kernel: the softplus terms of the chunks before; 0 for a whole list).
+__device__ __forceinline__ void hz_prefix(const double* a, double* logp, int S, int lane, double carry = 0.0) {
     for (int r0 = 0; r0 < S; r0 += 64) {
         const int s = r0 + lane;
         const double v = (s >= 1 && s < S) ? a[s - 1] : 0.0;
@@ -38,15 +40,10 @@ __device__ __forceinline__ void hz_prefix(const double* a, double* logp, int S, 
     }
 }
 
+// zs[s] = fp32 dot(x row of position s of list b, w) + bias (+ offset[s]) for s < S: wavefront wv takes the rows wv, wv+4, ..
 template <int V>
-__global__ __launch_bounds__(256) void hazard_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                         const float* __restrict__ bias, const float* __restrict__ offset,
-                                                         int S, int B, int E, float* __restrict__ p_out,
-                                                         float* __restrict__ stop_out, float* __restrict__ z_out) {
-    __shared__ float zs[MAXS];
-    __shared__ double sp[MAXS], logp[MAXS];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.x;
+__device__ __forceinline__ void hz_logits(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                          const float* __restrict__ offset, int S, int B, int E, int b, float* zs, int lane, int wv) {
     const int nch = E / (64 * V);
     float wr[MAXCH][V];
 #pragma unroll
@@ -67,6 +64,18 @@ __global__ __launch_bounds__(256) void hazard_fwd_kernel(const float* __restrict
         const float t = wave_sum(acc);
         if (lane == 0) zs[s] = offset ? (t + b0) + offset[s] : t + b0;
     }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void hazard_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                         const float* __restrict__ bias, const float* __restrict__ offset,
+                                                         int S, int B, int E, float* __restrict__ p_out,
+                                                         float* __restrict__ stop_out, float* __restrict__ z_out) {
+    __shared__ float zs[MAXS];
+    __shared__ double sp[MAXS], logp[MAXS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x;
+    hz_logits<V>(x, w, bias, offset, S, B, E, b, zs, lane, wv);
     __syncthreads();
     const size_t o = (size_t)b * S;
     for (int s = threadIdx.x; s < S; s += 256) {
@@ -182,6 +191,59 @@ __global__ __launch_bounds__(256) void hazard_bwd_kernel(const float* __restrict
     if (threadIdx.x == 0) prow[E] = dbs;
 }
 
+// The forward for a CHUNK of C positions t0 .. t0+C-1 (rlt_hazard_head_append): the dot and the float64 terms of hazard_fwd_kernel,
+// the prefix sum started from the list's carried L = -sum_{j<t0} softplus(z_j) and continued in position order; the last row is
+// the remainder only under `final`.  logp has one slot behind the chunk: what the prefix leaves there is the carry of the next
+// chunk.  With `active` the stop decision is taken here - the first row whose stop probability, widened to float64, is >= tau:
+// the comparison of rlt_cut_sweep's FIRST_ABOVE rule (csrc/sweep.hip:114, `x[r] >= th` on the value widened at sweep.hip:95) - and a
+// retired list leaves before it reads or writes anything.
+template <int V>
+__global__ __launch_bounds__(256) void hazard_append_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, const float* __restrict__ offset,
+                                                            int t0, int C, int B, int E, int final, double* __restrict__ carry,
+                                                            double tau, int32_t* __restrict__ active, int32_t* __restrict__ k_out,
+                                                            float* __restrict__ stop_out, float* __restrict__ p_out,
+                                                            float* __restrict__ z_out) {
+    __shared__ float zs[MAXS], st[MAXS];
+    __shared__ double sp[MAXS + 1], logp[MAXS + 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x;
+    if (active && active[b] == 0) return;          // block-uniform
+    hz_logits<V>(x, w, bias, offset, C, B, E, b, zs, lane, wv);
+    __syncthreads();
+    const size_t o = (size_t)b * C;
+    for (int s = threadIdx.x; s < C; s += 256) {
+        const float zf = zs[s];
+        const HzTerms t = hz_terms((double)zf);
+        const bool last = final && s == C - 1;
+        sp[s] = t.softplus;
+        logp[s] = last ? 0.0 : t.logsig;
+        const float sf = last ? 1.f : (float)t.h;
+        st[s] = sf;
+        stop_out[o + s] = sf;
+        if (z_out) z_out[o + s] = zf;
+    }
+    if (threadIdx.x == 0) { sp[C] = 0.0; logp[C] = 0.0; }
+    __syncthreads();
+    if (wv == 0) {
+        hz_prefix(sp, logp, C + 1, lane, -carry[b]);
+        if (active) {
+            int first = -1;                          // 0-based inside the chunk
+            for (int r0 = 0; r0 < C && first < 0; r0 += 64) {
+                const int s = r0 + lane;
+                const unsigned long long hit = __ballot(s < C && (double)st[s < C ? s : 0] >= tau);
+                if (hit != 0ull) first = r0 + (__ffsll((long long)hit) - 1);
+            }
+            if (first < 0 && final) first = C - 1;   // the list ends here: rlt_cut_sweep's "S if there is none"
+            if (first >= 0 && lane == 0) { k_out[b] = t0 + first + 1; active[b] = 0; }
+        }
+    }
+    __syncthreads();
+    if (p_out)
+        for (int s = threadIdx.x; s < C; s += 256) p_out[o + s] = (float)exp(logp[s]);
+    if (threadIdx.x == 0) carry[b] = logp[C];
+}
+
 bool hazard_dims_ok(int S, int E) { return S <= MAXS && E % 64 == 0 && E / (64 * pick_v(E)) <= MAXCH; }
 
 }  // namespace
@@ -199,6 +261,22 @@ int rlt_hazard_head_fwd(const float* x, const float* w, const float* b, const fl
     if (V == 4) hipLaunchKernelGGL(hazard_fwd_kernel<4>, grid, block, 0, st, x, w, b, offset, S, B, E, p, stop, z);
     else if (V == 2) hipLaunchKernelGGL(hazard_fwd_kernel<2>, grid, block, 0, st, x, w, b, offset, S, B, E, p, stop, z);
     else hipLaunchKernelGGL(hazard_fwd_kernel<1>, grid, block, 0, st, x, w, b, offset, S, B, E, p, stop, z);
+    return RLT_LAUNCH_RESULT();
+}
+
+int rlt_hazard_head_append(const float* x, const float* w, const float* b, const float* offset, int t0, int C, int B, int E,
+                           int final, double* carry, double tau, int32_t* active, int32_t* k, float* stop, float* p, float* z,
+                           void* stream) {
+    RLT_CHECK_ARG(x && w && b && carry && stop && (!active || k) && C > 0 && B > 0 && E > 0);
+    RLT_CHECK_ARG(t0 >= 0 && t0 <= INT_MAX - C);
+    RLT_CHECK_SHAPE(hazard_dims_ok(C, E));
+    if (!(rlt_aligned16(x) && rlt_aligned16(w))) return RLT_E_ALIGN;
+    const int V = pick_v(E);
+    hipStream_t st = rlt_stream(stream);
+    dim3 grid(B), block(256);
+    if (V == 4) hipLaunchKernelGGL(hazard_append_kernel<4>, grid, block, 0, st, x, w, b, offset, t0, C, B, E, final, carry, tau, active, k, stop, p, z);
+    else if (V == 2) hipLaunchKernelGGL(hazard_append_kernel<2>, grid, block, 0, st, x, w, b, offset, t0, C, B, E, final, carry, tau, active, k, stop, p, z);
+    else hipLaunchKernelGGL(hazard_append_kernel<1>, grid, block, 0, st, x, w, b, offset, t0, C, B, E, final, carry, tau, active, k, stop, p, z);
     return RLT_LAUNCH_RESULT();
 }
 

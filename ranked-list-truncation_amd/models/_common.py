@@ -207,6 +207,19 @@ class CutModel(nn.Module):
             per, _ = ops.cut_report(cut)
         return per["k"], per["p_k"]
 
+    # why a class cannot be streamed a page of ranks at a time (Choopy overrides `stream`)
+    _NO_STREAM = {"AttnCut": "its BiLSTM runs over the list in both directions, so every rank reads the ranks below it",
+                  "MtAttnCut": "its BiLSTM runs both ways and its multi-task heads normalise over the whole list",
+                  "MtChoopy": "its multi-task heads (softmax re-ranking, classification) normalise over the whole list",
+                  "BiCut": "its BiLSTM runs over the list in both directions"}
+
+    def stream(self, tau, batch_size):
+        """Only a Choopy with attention_axis='position', attention_mask='causal', cut_head='hazard' can truncate online
+        (utils/stream.py); every other model raises ValueError saying why."""
+        why = self._NO_STREAM.get(type(self).__name__, "its output at a rank is not computed from the ranks above it alone")
+        raise ValueError(f"{type(self).__name__} cannot stream: {why} (use Choopy with attention_axis='position', "
+                         "attention_mask='causal', cut_head='hazard')")
+
     _TOWER_HEADS = {"TowerClass": "classi", "TowerRerank": "rerank", "TowerCut": "decison_layer"}
 
     def head_names(self):

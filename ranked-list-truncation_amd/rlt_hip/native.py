@@ -117,6 +117,8 @@ _SIGNATURES = {
     "rlt_seq_attention_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_size_t, c_int, P]),
     "rlt_seq_attention_fwd_ex": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_int, P]),
     "rlt_seq_attention_bwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_size_t, c_int, P]),
+    # streaming: the causal forward one chunk of ranks at a time over a K/V cache (csrc/attention_seq_append.hip)
+    "rlt_seq_attention_append": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
     "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
@@ -131,6 +133,7 @@ _SIGNATURES = {
     "rlt_hazard_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     "rlt_hazard_head_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
     "rlt_hazard_head_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
+    "rlt_hazard_head_append": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_double, P, P, P, P, P, P]),
     "rlt_mmoe_gate_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rlt_mmoe_gate_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "rlt_mmoe_gate_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_size_t, P]),

@@ -365,6 +365,64 @@ def seq_attention(qkv, S, B, H, drop_p=0.0, causal=False):
     return SeqAttentionFn.apply(N.f32c(qkv), S, B, H, drop_p, next_seed() if drop_p > 0 else 0, causal)
 
 
+def _check_active(active, B, like, what):
+    if active is None:
+        return
+    if active.dtype != torch.int32 or active.shape != (B,) or not active.is_contiguous() or active.device != like.device:
+        raise ValueError(f"{what}: active must be a contiguous int32 tensor of shape ({B},) on {like.device}")
+
+
+def seq_attention_append(qkv_chunk, cache, t0, C, Smax, B, H, active=None, want_lse=False):
+    """Streaming (inference only, no tape): the causal within-list attention of the C new ranks t0 .. t0+C-1 over a K/V cache
+    (rlt_seq_attention_append).  qkv_chunk (C*B, 3E) position-major, cache (Smax*B, 2E) fp32 - written in place at rows
+    t0 .. t0+C-1, read below t0 -, active (B,) int32 or None.  -> out (C*B, E), or (out, lse (B,H,C)) with want_lse.  The rows of a
+    retired list (active[b] == 0) are not written: out is zero there when `active` is given, lse is not initialised."""
+    N.require_cuda(qkv_chunk)
+    E = qkv_chunk.shape[1] // 3
+    if qkv_chunk.dtype != torch.float32 or not qkv_chunk.is_contiguous() or qkv_chunk.shape != (C * B, 3 * E) or E % H:
+        raise ValueError(f"seq_attention_append: qkv_chunk {tuple(qkv_chunk.shape)} is not C*B = {C * B} contiguous fp32 rows of 3 * H * HD columns")
+    if cache.dtype != torch.float32 or not cache.is_contiguous() or cache.shape != (Smax * B, 2 * E) or cache.device != qkv_chunk.device:
+        raise ValueError(f"seq_attention_append: the cache must be a contiguous fp32 ({Smax * B}, {2 * E}) tensor on {qkv_chunk.device}, got {tuple(cache.shape)}")
+    if t0 < 0 or C < 1 or t0 + C > Smax:
+        raise ValueError(f"seq_attention_append: ranks {t0} .. {t0 + C - 1} do not lie inside a list of {Smax}")
+    _check_active(active, B, qkv_chunk, "seq_attention_append")
+    out = _empty((C * B, E), qkv_chunk) if active is None else torch.zeros((C * B, E), dtype=torch.float32, device=qkv_chunk.device)
+    lse = _empty((B, H, C), qkv_chunk) if want_lse else None
+    _launch("seq_attn_append", lambda: call("rlt_seq_attention_append", ptr(qkv_chunk), ptr(cache), t0, C, Smax, B, H, E // H, ptr(active),
+                                            ptr(out), ptr(lse), current_precision(), stream()))
+    return (out, lse) if want_lse else out
+
+
+def encoder_layer_append(x_chunk, layer, cache, t0, Smax, B, H, active=None, eps=1e-5):
+    """Streaming (inference only): the eval-mode encoder layer of EncoderLayerKernelsFn._forward on the C*B rows of a chunk of
+    ranks t0 .. t0+C-1, with rlt_seq_attention_append over the layer's K/V `cache` (Smax*B, 2E) in the attention slot: in_proj,
+    attention, out_proj, residual + LayerNorm, the FFN pair, residual + LayerNorm.  Nothing is stashed (no 1-bit ReLU mask, no
+    tape).  The GEMMs and LayerNorms run over ALL C*B rows; only the attention skips the lists `active` retires.  -> (C*B, E)."""
+    T, E = x_chunk.shape
+    if T % B:
+        raise ValueError(f"encoder_layer_append: {T} rows are not a whole number of ranks of {B} lists")
+    C = T // B
+    att_p = layer.self_attn
+    w1, w2 = layer.linear1.weight, layer.linear2.weight
+    Fh = w1.shape[0]
+    with torch.no_grad():
+        x = N.f32c(x_chunk)
+        qkv = _empty((T, 3 * E), x)
+        gemm(0, 1, T, 3 * E, E, x, E, att_p.in_proj_weight, E, qkv, 3 * E, bias=att_p.in_proj_bias)
+        att = seq_attention_append(qkv, cache, t0, C, Smax, B, H, active)
+        proj = _empty((T, E), x)
+        gemm(0, 1, T, E, E, att, E, att_p.out_proj.weight, E, proj, E, bias=att_p.out_proj.bias)
+        h1, st = _empty((T, E), x), _empty((T, 2), x)
+        call("rlt_add_layernorm_fwd", ptr(x), ptr(proj), ptr(layer.norm1.weight), ptr(layer.norm1.bias), T, E, eps, 0.0, 0, ptr(h1), ptr(st), stream())
+        hid = _empty((T, Fh), x)
+        gemm(0, 1, T, Fh, E, h1, E, w1, E, hid, Fh, bias=layer.linear1.bias, flags=N.GEMM_RELU)
+        ff = _empty((T, E), x)
+        gemm(0, 1, T, E, Fh, hid, Fh, w2, Fh, ff, E, bias=layer.linear2.bias)
+        y = _empty((T, E), x)
+        call("rlt_add_layernorm_fwd", ptr(h1), ptr(ff), ptr(layer.norm2.weight), ptr(layer.norm2.bias), T, E, eps, 0.0, 0, ptr(y), ptr(st), stream())
+    return y
+
+
 # ------------------------------------------------------------------------------ whole encoder layer
 class EncoderLayerFn(Function):
     """One post-norm nn.TransformerEncoderLayer (list-axis attention, ReLU FFN) as ONE tape node on the path-level
@@ -965,6 +1023,43 @@ def hazard_head(x_pm, weight, bias, S, B, offset=None):
             raise ValueError(f"hazard_head: offset must have S = {S} elements, got {tuple(offset.shape)}")
         offset = N.f32c(offset.detach())
     return HazardHeadFn.apply(N.f32c(x_pm), N.f32c(weight.reshape(1, E)), N.f32c(bias.reshape(1)), offset, S, B)
+
+
+def hazard_head_append(x_pm, weight, bias, t0, B, carry, tau=1.0, final=False, active=None, k=None, offset=None, want_p=False,
+                       want_z=False):
+    """Streaming (inference only, no tape): the hazard head on a chunk of positions t0 .. t0+C-1 (rlt_hazard_head_append).
+    x_pm (C*B, E) position-major; carry (B,) float64, in place: zeros before the chunk at t0 = 0; offset (C,): the chunk's slice
+    of the prior offset, or None; final: the chunk ends the list.  With active (B,) int32 and k (B,) int32, both in place, the
+    stop decision is taken on the device: the first row with stop >= tau (cut_sweep's 'above' comparison) writes k = its 1-based
+    rank and clears active; under final every list still active stops at the last row.  -> {'stop', 'p', 'z'}: (B, C) each, p and
+    z None unless asked for.  The rows of a list that was retired on entry are not written: they are NaN."""
+    N.require_cuda(x_pm)
+    T, E = x_pm.shape
+    if T % B or T == 0:
+        raise ValueError(f"hazard_head_append: {T} rows are not a whole number of positions of {B} lists")
+    C = T // B
+    if weight.numel() != E or bias.numel() != 1:
+        raise ValueError(f"hazard_head_append: one weight row of {E} and one bias, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    if carry.dtype != torch.float64 or carry.shape != (B,) or not carry.is_contiguous() or carry.device != x_pm.device:
+        raise ValueError(f"hazard_head_append: carry must be a contiguous float64 tensor of shape ({B},) on {x_pm.device}")
+    if (active is None) != (k is None):
+        raise ValueError("hazard_head_append: pass both `active` and `k`, or neither")
+    _check_active(active, B, x_pm, "hazard_head_append")
+    if k is not None and (k.dtype != torch.int32 or k.shape != (B,) or not k.is_contiguous() or k.device != x_pm.device):
+        raise ValueError(f"hazard_head_append: k must be a contiguous int32 tensor of shape ({B},) on {x_pm.device}")
+    if offset is not None:
+        if offset.numel() != C:
+            raise ValueError(f"hazard_head_append: offset must have C = {C} elements (the chunk's slice), got {tuple(offset.shape)}")
+        offset = N.f32c(offset.detach())
+    if t0 < 0:
+        raise ValueError(f"hazard_head_append: t0 = {t0} is negative")
+    x = N.f32c(x_pm.detach())
+    w, b = N.f32c(weight.detach().reshape(1, E)), N.f32c(bias.detach().reshape(1))
+    new = (lambda: _empty((B, C), x)) if active is None else (lambda: torch.full((B, C), float("nan"), dtype=torch.float32, device=x.device))
+    stop, p, z = new(), (new() if want_p else None), (new() if want_z else None)
+    _launch("hazard_append", lambda: call("rlt_hazard_head_append", ptr(x), ptr(w), ptr(b), ptr(offset), t0, C, B, E, 1 if final else 0,
+                                          ptr(carry), float(tau), ptr(active), ptr(k), ptr(stop), ptr(p), ptr(z), stream()))
+    return {"stop": stop, "p": p, "z": z}
 
 
 # ------------------------------------------------------------------------------ MMOE

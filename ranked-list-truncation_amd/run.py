@@ -670,6 +670,31 @@ class Trainer:
                 np.savez(out_path, summary=np.asarray(json.dumps(results)), lengths=np.asarray(sorted(map(int, results))), **arrays)
         return results
 
+    def stream_eval(self, page, tau):
+        """--stream-eval: the test split once more, a page of `page` ranks at a time through model.stream; the lists of a
+        bucket whose length is not the model's seq_len cannot be streamed and are an error.  Means over the lists: the streamed
+        cut, F1 and DCG at it (ops.cut_metrics with k_in) and the ranks read (whole pages up to the stop).  No collective: rank
+        0 calls it.  One host read per batch, after its last page."""
+        n, tot = 0, [0.0, 0.0, 0.0, 0.0]
+        for X, y in self.test_loader:
+            B, S = int(X.shape[0]), int(X.shape[1])
+            if S != self.model.seq_len:
+                raise ValueError(f"--stream-eval: a test bucket of length {S} does not match the model's seq_len {self.model.seq_len}")
+            st = self.model.stream(tau, B)
+            scores = X.to(self.device, non_blocking=True)[..., :1].contiguous()
+            for t0 in range(0, S, page):
+                st.push(scores[:, t0:t0 + page].contiguous())
+            k = st.k
+            _, f1, dcg, _ = ops.cut_metrics(None, y.to(self.device, non_blocking=True).float().contiguous(), k_in=k)
+            vals = torch.stack([k.double().sum(), f1.sum(), dcg.sum(), st.documents_read().double().sum()]).tolist()
+            tot = [a + b for a, b in zip(tot, vals)]
+            n += B
+        res = {"stream_page": int(page), "stream_tau": float(tau), "stream_lists": n, "stream_k": tot[0] / n, "stream_f1": tot[1] / n,
+               "stream_dcg": tot[2] / n, "stream_read": tot[3] / n}
+        logging.info('\tStreamed test (pages of {}, tau = {}): cut = {:.3f} | f1 = {:.6f} | dcg = {:.6f} | ranks read = {:.3f}\n'.format(
+            page, tau, res["stream_k"], res["stream_f1"], res["stream_dcg"], res["stream_read"]))
+        return res
+
     def draw(self, epoch):
         """--draw 1 (run.py:188): for every test batch of more than 40 lists, the two curves `Trainer.plot` draws (run.py:262-283,
         tau = 0.9) into the scalar log.  The batches are the test buckets in file order."""
@@ -706,6 +731,8 @@ class Trainer:
                     self.compare_lines = self.compare(self.args.report_out, self.args.compare_to)
             if getattr(self.args, "cut_sweep", None) and self.rank == 0:
                 self.sweep_results = self.cut_sweep(self.args.cut_sweep, getattr(self.args, "sweep_out", None))
+            if getattr(self.args, "stream_eval", 0) and self.rank == 0:
+                self.stream_results = self.stream_eval(self.args.stream_eval, getattr(self.args, "stream_tau", 0.5))
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -835,6 +862,11 @@ def build_parser():
     p.add_argument('--hazard-prior', type=str, default='uniform', choices=('uniform', 'none'),
                    help="fixed offset of the hazard head's logits: 'uniform' = -log(S-1-s), under which zero weights give the uniform "
                         "cut distribution (without it they give a geometric one with mean 2, which cannot reach long cuts)")
+    p.add_argument('--stream-eval', type=int, default=0, metavar='C',
+                   help="choopy with --attention-axis position --attention-mask causal --cut-head hazard only: after the last epoch "
+                        "walk the test split in pages of C ranks through model.stream (utils/stream.py) and log the mean cut, F1 and "
+                        "DCG at the streamed cut and the mean ranks read; `stream_*` keys in --history-json.  0 = off")
+    p.add_argument('--stream-tau', type=float, default=0.5, help="the stop threshold of --stream-eval (truncate's rule 'above')")
     p.add_argument('--history-json', type=str, default=None, help="rank 0 writes the per-epoch train / test means and the best / best-5 figures here")
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "
@@ -926,6 +958,12 @@ def main(argv=None):
         eval_reward_spec(args)
     except ValueError as e:
         parser.error(str(e))
+    if args.stream_eval < 0:
+        parser.error("--stream-eval takes a positive page size (0 = off)")
+    if args.stream_eval and not (args.model_name == "choopy" and args.attention_axis == "position" and args.attention_mask == "causal"
+                                 and args.cut_head == "hazard"):
+        parser.error("--stream-eval needs --model-name choopy --attention-axis position --attention-mask causal --cut-head hazard "
+                     "(only that model computes rank i from the ranks above it)")
     if args.attention_mask == "causal" and args.attention_axis != "position":
         parser.error("--attention-mask causal needs --attention-axis position (the list axis attends across lists, not positions)")
     # RLT_FORCE_DIST=1: initialise the process group (and run the step's collectives) even with one rank - the RCCL
@@ -959,7 +997,7 @@ def main(argv=None):
             fin = lambda v: v if v is not None and math.isfinite(v) else None     # -inf (no test epoch) is not valid JSON
             json.dump({"history": trainer.history, "best_f1": fin(trainer.best_test_f1), "best_dcg": fin(trainer.best_test_dcg),
                        "best5_f1": fin(trainer.best5_f1), "best5_dcg": fin(trainer.best5_dcg), "best_epoch": trainer.best_epoch,
-                       "world": trainer.world, "attention_axis": trainer.attention_axis, **trainer._mask_record(), **({"baselines": trainer.baseline_results} if args.baselines else {}),
+                       "world": trainer.world, "attention_axis": trainer.attention_axis, **trainer._mask_record(), **getattr(trainer, "stream_results", {}), **({"baselines": trainer.baseline_results} if args.baselines else {}),
                        **({"eval_reward": {"spec": eval_reward_text(eval_reward_spec(args)),
                                            "report": getattr(trainer, "report_results", None),
                                            "cut_sweep": getattr(trainer, "sweep_results", None)}} if eval_reward_spec(args) else {})}, f)

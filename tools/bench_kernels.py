@@ -1649,8 +1649,110 @@ def hazard(shapes=((4096, 300, 256), (8192, 300, 128)), reps=7, runs=2):
         torch.cuda.empty_cache()
 
 
+def _once_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def stream_bench(reps=7, runs=2, S=300, pages=(1, 10, 32)):
+    """Streaming truncation (rlt_seq_attention_append, rlt_hazard_head_append, utils/stream.py): the total time to stream S = 300 ranks
+    in pages of 1, 10 and 32, the median of `reps` HIP-event timings in each of `runs` runs, against two yardsticks measured in the
+    same job with the one-shot kernels:
+      (a) ONE one-shot causal forward of the whole list - the floor: streaming does the same arithmetic in more launches;
+      (b) one one-shot causal forward PER PAGE - what a caller has to do without the streaming calls (at page 1 that is 300
+          forwards: the model-level figure is one timing per run, not a median).
+    Two configurations: the whole model (Choopy, 8192 lists, E 128, 8 heads, 3 layers: model.stream against
+    model.stop_probabilities) and the attention alone (4096 lists, 4 heads of 64).  At page 10 a second line retires every other
+    list at rank 30.  Last, the append kernel alone at C = 1, t0 = 299, as GB/s on its 8 t B E bytes of cache."""
+    import models as hm
+    D = N.PRECISION_DEFAULT
+    npages = lambda c: (S + c - 1) // c
+    # ---- the attention alone
+    B, H, HD = 4096, 4, 64
+    E = H * HD
+    qkv = torch.randn(S * B, 3 * E, device=dev)
+    out, lse = torch.empty(S * B, E, device=dev), torch.empty(B, H, S, device=dev)
+    cache = torch.empty(S * B, 2 * E, device=dev)
+    ones = torch.ones(B, dtype=torch.int32, device=dev)
+    half = ones.clone()
+    half[::2] = 0
+    upper = ones.clone()
+    upper[B // 2:] = 0
+    one_shot = lambda: call("rlt_seq_attention_fwd_ex", ptr(qkv), S, B, H, HD, 0.0, 0, N.SEQ_MASK_CAUSAL, ptr(out), ptr(lse), D, stream())
+
+    def append(t0, c, active=None):
+        call("rlt_seq_attention_append", N.c_void_p(qkv.data_ptr() + 4 * t0 * B * 3 * E), ptr(cache), t0, c, S, B, H, HD, ptr(active),
+             N.c_void_p(out.data_ptr() + 4 * t0 * B * E), ptr(lse), D, stream())
+
+    def attn_stream(c, retire_at=None):
+        for t0 in range(0, S, c):
+            append(t0, min(c, S - t0), None if retire_at is None else (ones if t0 < retire_at else half))
+
+    def per_page(fn, c):
+        for _ in range(npages(c)):
+            fn()
+
+    for r in range(runs):
+        a = _seq_median_ms(one_shot, reps)
+        print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} (a) one-shot causal forward: {a:9.3f} ms", flush=True)
+        for c in pages:
+            s, b = _seq_median_ms(lambda: attn_stream(c), reps), _seq_median_ms(lambda: per_page(one_shot, c), reps)
+            print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} page {c:2d}: streamed {s:9.3f} ms = {s / a:6.2f} x (a) | (b) {npages(c)} one-shot "
+                  f"forwards {b:9.3f} ms | (b) / streamed {b / s:6.2f} x", flush=True)
+        s = _seq_median_ms(lambda: attn_stream(10, 30), reps)
+        print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} page 10, every other list retired at rank 30: {s:9.3f} ms", flush=True)
+        t = _seq_median_ms(lambda: append(S - 1, 1), reps)
+        print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} append alone C 1 t0 {S - 1}: {t * 1e3:9.1f} us  "
+              f"{8 * (S - 1) * B * E / t / 1e6:8.1f} GB/s on 8 t B E", flush=True)
+        for what, act in (("every other list retired", half), ("the second half of the lists retired", upper)):
+            t = _seq_median_ms(lambda: append(S - 1, 1, act), reps)
+            print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} append alone C 1 t0 {S - 1}, {what}: {t * 1e3:9.1f} us  "
+                  f"{8 * (S - 1) * (B // 2) * E / t / 1e6:8.1f} GB/s on 8 t (B/2) E", flush=True)
+    # the append kernel alone at head dim 16 (Choopy's heads)
+    del qkv, out, cache
+    B, H, HD = 8192, 8, 16
+    E = H * HD
+    qkv, out, cache = torch.randn(B, 3 * E, device=dev), torch.empty(B, E, device=dev), torch.randn(S * B, 2 * E, device=dev)
+    for r in range(runs):
+        t = _seq_median_ms(lambda: call("rlt_seq_attention_append", ptr(qkv), ptr(cache), S - 1, 1, S, B, H, HD, None, ptr(out), None, D, stream()), reps)
+        print(f"stream attention B{B} S{S} H{H} HD{HD} run {r} append alone C 1 t0 {S - 1}: {t * 1e3:9.1f} us  "
+              f"{8 * (S - 1) * B * E / t / 1e6:8.1f} GB/s on 8 t B E", flush=True)
+    del qkv, out, cache
+    torch.cuda.empty_cache()
+    # ---- the whole model
+    torch.manual_seed(3)
+    m = hm.Choopy(seq_len=S, d_model=128, n_head=8, num_layers=3, dropout=0.0, attention_axis="position", attention_mask="causal",
+                  cut_head="hazard").to(dev).eval()
+    x = torch.randn(B, S, 1, device=dev)
+    st = m.stream(2.0, B)                                           # tau = 2: nothing stops before the end
+    chunks = {c: [x[:, t0:t0 + c].contiguous() for t0 in range(0, S, c)] for c in pages}
+    forward = lambda: m.stop_probabilities(x)
+
+    def model_stream(c, retire_at=None):
+        st.reset()
+        for page in chunks[c]:
+            if retire_at is not None and st.position == retire_at:
+                st.active[::2] = 0
+            st.push(page)
+
+    for r in range(runs):
+        a = _seq_median_ms(forward, reps)
+        print(f"stream choopy B{B} S{S} E128 H8 L3 run {r} (a) one-shot forward (stop_probabilities): {a:9.3f} ms", flush=True)
+        for c in pages:
+            s = _seq_median_ms(lambda: model_stream(c), reps)
+            b = _seq_median_ms(lambda: per_page(forward, c), reps) if c > 1 else _once_ms(lambda: per_page(forward, c))
+            print(f"stream choopy B{B} S{S} E128 H8 L3 run {r} page {c:2d}: streamed {s:9.3f} ms = {s / a:6.2f} x (a) | (b) {npages(c)} one-shot "
+                  f"forwards {b:9.3f} ms{' (one timing)' if c == 1 else ''} | (b) / streamed {b / s:6.2f} x", flush=True)
+        s = _seq_median_ms(lambda: model_stream(10, 30), reps)
+        print(f"stream choopy B{B} S{S} E128 H8 L3 run {r} page 10, every other list retired at rank 30: {s:9.3f} ms", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
     for w in which:
-        globals()[w]()
+        {"stream": stream_bench}.get(w, globals()[w])()          # (`stream` itself is the library's stream getter)
