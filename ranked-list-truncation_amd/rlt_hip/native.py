@@ -6,174 +6,43 @@ a raw device pointer.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p  # noqa: F401  (ops.py and the tests use them as N.c_*)
 
 import torch
 
+from . import header
+
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("RLT_HIP_LIB") or os.path.join(_PKG, "csrc", "librlt_hip.so")   # env override: kernel experiments
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "rlt_hip.h")
 
-# constants of include/rlt_hip.h
-METRIC_F1, METRIC_DCG = 0, 1
-LOSS_EXPECT, LOSS_CE, LOSS_KL, LOSS_JS = 0, 1, 2, 3
-GEMM_RELU, GEMM_ACCUMULATE = 1, 2
-HEAD_SOFTMAX, HEAD_SIGMOID, HEAD_IDENTITY = 0, 1, 2
-PROBE_BCE, PROBE_RERANK = 0, 1
-CUT_ARGMAX, CUT_PAIR = 0, 1
-SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE = 0, 1, 2
-SWEEP_COLS, SWEEP_MAX_T = 8, 64
-REWARD_FBETA, REWARD_GAIN, REWARD_MAX_GRADES = 0, 1, 8
-PAIR_RANKNET, PAIR_LAMBDARANK = 0, 1
-SEQ_MASK_NONE, SEQ_MASK_CAUSAL = 0, 1
+# the header is the one statement of the ABI: its integer #defines, the (restype, [argtypes]) of every prototype, its struct bodies
+DEFINES, _SIGNATURES, STRUCTS = header.read(HEADER_PATH)
+EXPORTS = tuple(_SIGNATURES)
+
+
+def _rlt(prefix, names):
+    return tuple(DEFINES[f"RLT_{prefix}_{n}"] for n in names.split())
+
+
+ABI_VERSION = DEFINES["RLT_ABI_VERSION"]
+METRIC_F1, METRIC_DCG = _rlt("METRIC", "F1 DCG")
+LOSS_EXPECT, LOSS_CE, LOSS_KL, LOSS_JS = _rlt("LOSS", "EXPECT CE KL JS")
+GEMM_RELU, GEMM_ACCUMULATE = _rlt("GEMM", "RELU ACCUMULATE")
+HEAD_SOFTMAX, HEAD_SIGMOID, HEAD_IDENTITY = _rlt("HEAD", "SOFTMAX SIGMOID IDENTITY")
+PROBE_BCE, PROBE_RERANK = _rlt("PROBE", "BCE RERANK")
+CUT_ARGMAX, CUT_PAIR = _rlt("CUT", "ARGMAX PAIR")
+SWEEP_QUANTILE, SWEEP_FIRST_BELOW, SWEEP_FIRST_ABOVE, SWEEP_COLS = _rlt("SWEEP", "QUANTILE FIRST_BELOW FIRST_ABOVE COLS")
+SWEEP_MAX_T = 64                                                                          # rlt_cut_sweep: T <= 64, stated in words only
+REWARD_FBETA, REWARD_GAIN, REWARD_MAX_GRADES = _rlt("REWARD", "FBETA GAIN MAX_GRADES")
+PAIR_RANKNET, PAIR_LAMBDARANK = _rlt("PAIR", "RANKNET LAMBDARANK")
+SEQ_MASK_NONE, SEQ_MASK_CAUSAL = _rlt("SEQ_MASK", "NONE CAUSAL")
 PAIR_KINDS = {"ranknet": PAIR_RANKNET, "lambdarank": PAIR_LAMBDARANK}
 SWEEP_ROWS = ("k", "f1", "dcg", "precision", "recall", "fbeta", "uncut", "n_lists")      # the rows of rlt_cut_sweep's curve
-PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = -1, 0, 1, 2
+PRECISION_DEFAULT, PRECISION_FP32, PRECISION_BF16X3, PRECISION_BF16X6 = _rlt("PRECISION", "DEFAULT FP32 BF16X3 BF16X6")
 _PRECISION_NAMES = {PRECISION_FP32: "fp32", PRECISION_BF16X3: "bf16x3", PRECISION_BF16X6: "bf16x6"}
-
-P = c_void_p
-_SIGNATURES = {
-    "rlt_abi_version": (c_int, []),
-    "rlt_error_string": (c_char_p, [c_int]),
-    "rlt_set_precision": (c_int, [c_int]),
-    "rlt_get_precision": (c_int, []),
-    "rlt_reward_loss": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),
-    "rlt_reward_matrix": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P, P]),
-    "rlt_reward_loss_ex": (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_int, c_float, P, P, P, P]),
-    "rlt_reward_matrix_ex": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, P, P]),
-    "rlt_loss_metrics_workspace": (c_size_t, [c_int]),
-    "rlt_dcg_table_bytes": (c_size_t, []),
-    "rlt_dcg_table_init": (c_int, [P, c_size_t, P]),
-    "rlt_loss_metrics": (c_int, [P, P, P, c_int, c_int, c_int, c_float, c_int, c_float, c_double, P, P, P, P, P, P, P, P, P, c_size_t, P]),
-    # reward losses for any cut reward (csrc/reward_any.hip)
-    "rlt_reward_spec_matrix": (c_int, [P, c_int, c_int, P, c_float, P, P, P, P]),
-    "rlt_reward_any_workspace": (c_size_t, [c_int]),
-    "rlt_reward_any_loss": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
-    # evaluation in any cut reward (csrc/reward_eval.hip)
-    "rlt_reward_eval_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "rlt_reward_eval": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
-    "rlt_cut_metrics_ex": (c_int, [P, P, P, c_int, c_int, c_double, P, P, P, P, P]),
-    "rlt_mt_terms_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_mt_terms": (c_int, [P, P, P, c_int, c_int, c_float, P, P, c_size_t, P]),
-    "rlt_mt_terms_bwd": (c_int, [P, P, P, c_int, c_int, c_float, c_float, P, P, P, P]),
-    "rlt_weighted_sum": (c_int, [P, P, c_int, P, P]),
-    "rlt_cut_metrics": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P]),
-    "rlt_wass_loss_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_wass_loss_fwd": (c_int, [P, P, c_int, c_int, c_float, c_int, c_float, P, P, c_size_t, P]),
-    "rlt_wass_loss_bwd": (c_int, [P, P, P, c_int, c_int, c_float, c_int, P, c_size_t, P, P]),
-    "rlt_task_metrics": (c_int, [P, P, c_int, c_int, P, P, P, P]),
-    # stable per-list sort by a head's values, the companion arrays carried along (csrc/rerank.hip)
-    "rlt_rerank_lists": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P, P]),
-    # RankNet / LambdaRank on a rerank head's scores, with the counting rank (csrc/pair_rank.hip)
-    "rlt_pair_rank_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_pair_rank_loss": (c_int, [P, P, c_int, c_int, c_int, c_float, P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
-    "rlt_truncation_curves_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_truncation_curves": (c_int, [P, c_int, c_int, c_double, P, c_int, P, P, P, P, P, P, P, c_size_t, P]),
-    "rlt_cut_report_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_cut_report": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_float, c_double, c_double, c_double, P, c_int,
-                               P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P]),
-    # threshold cut rules and the effectiveness / cost curve (csrc/sweep.hip)
-    "rlt_cut_sweep_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "rlt_cut_sweep": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_int, c_double, c_double, P, c_int, P, P, P, c_size_t, P]),
-    "rlt_probe_heads_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "rlt_probe_heads": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_float, P, P, P, P, P, c_size_t, P]),
-    "rlt_neighbor_features": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P, c_int, c_int, P]),
-    "rlt_pair_softmax_fwd": (c_int, [P, c_int, c_int, c_float, c_uint32, P, P]),
-    "rlt_pair_softmax_bwd": (c_int, [P, P, c_int, c_int, c_float, c_uint32, P, P]),
-    "rlt_bicut_loss": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),
-    "rlt_gemm_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "rlt_gemm_bits_words": (c_size_t, [c_int, c_int]),
-    "rlt_gemm_bits": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_float, c_uint32,
-                              P, P, c_float, c_int, P]),
-    "rlt_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, P, c_size_t, c_int, P]),
-    "rlt_gemm_ex": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P, P, c_int, P, c_int, c_float,
-                            P, c_float, c_uint32, P, c_size_t, c_int, P]),
-    "rlt_gemm_last_dispatch": (c_int, [P]),
-    "rlt_gemm_plan": (c_int, [P, c_int, P]),
-    "rlt_dropout_mask": (c_int, [c_uint32, c_size_t, c_int, c_float, P, P]),
-    "rlt_attention_dropout_mask": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
-    "rlt_attention_dropout_mask_range": (c_int, [c_uint32, c_int, c_int, c_int, c_float, P, P]),
-    "rlt_colsum_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_colsum": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_size_t, P]),
-    "rlt_segment_colsum": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
-    "rlt_narrow_dw_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_narrow_dw": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
-    "rlt_relu_bwd": (c_int, [P, P, c_size_t, P]),
-    "rlt_scale": (c_int, [P, P, c_size_t, P]),
-    "rlt_add_layernorm_fwd": (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_uint32, P, P, P]),
-    "rlt_add_layernorm_bwd_workspace": (c_size_t, [c_int, c_int]),
-    "rlt_add_layernorm_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_float, c_uint32, P, P, P, P, c_int, P, c_size_t, P]),
-    "rlt_list_attention_fwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_float, c_int]),
-    "rlt_list_attention_images_retained": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "rlt_list_attention_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, P, c_size_t, c_int, P]),
-    "rlt_list_attention_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_float, c_int]),
-    "rlt_list_attention_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, P, c_size_t, c_int, P]),
-    "rlt_list_attention_bwd_prepare": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, c_size_t, c_int, P]),
-    "rlt_list_attention_bwd_dkv": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
-    "rlt_list_attention_bwd_dq": (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_uint32, P, c_int, P]),
-    "rlt_list_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_float, c_int, c_int, P]),
-    # within-list ("position-axis") attention (csrc/attention_seq.hip)
-    "rlt_seq_attention_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_float, c_int]),
-    "rlt_seq_attention_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_int, P]),
-    "rlt_seq_attention_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, P, P, c_size_t, c_int, P]),
-    "rlt_seq_attention_fwd_ex": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_int, P]),
-    "rlt_seq_attention_bwd_ex": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_uint32, c_int, P, P, c_size_t, c_int, P]),
-    # streaming: the causal forward one chunk of ranks at a time over a K/V cache (csrc/attention_seq_append.hip)
-    "rlt_seq_attention_append": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P]),
-    "rlt_bilstm_rec_fwd": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P]),
-    "rlt_bilstm_rec_fwd_x": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
-    "rlt_bilstm_rec_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
-    "rlt_bilstm_rec_plan": (c_int, [c_int, c_int, c_int, P]),
-    "rlt_to_position_major": (c_int, [P, c_int, c_int, c_int, P, P]),
-    "rlt_from_position_major": (c_int, [P, c_int, c_int, c_int, P, P]),
-    "rlt_choopy_embed": (c_int, [P, P, c_int, c_int, c_int, P, P]),
-    "rlt_heads_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
-    "rlt_heads_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "rlt_heads_bwd": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
-    # hazard cut head: stop probabilities and the cut distribution they imply (csrc/hazard.hip)
-    "rlt_hazard_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
-    "rlt_hazard_head_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "rlt_hazard_head_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
-    "rlt_hazard_head_append": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_double, P, P, P, P, P, P]),
-    "rlt_mmoe_gate_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "rlt_mmoe_gate_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "rlt_mmoe_gate_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_size_t, P]),
-    "rlt_mmoe_mix_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "rlt_mmoe_mix_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
-    "rlt_adam_step": (c_int, [P, P, P, P, c_size_t, c_int, c_float, c_float, c_float, c_float, c_float, P]),
-    # guarded optimizer step: gradient norms, clipping, non-finite skip (csrc/optim.hip)
-    "rlt_grad_norm_chunk": (c_size_t, []),
-    "rlt_grad_norm_grid": (c_int, []),
-    "rlt_grad_norm_workspace": (c_size_t, [c_size_t, c_int]),
-    "rlt_grad_norm": (c_int, [P, c_size_t, P, c_int, c_float, P, c_size_t, P, P, P]),
-    "rlt_adam_step_guarded": (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
-    # training recipe in one Adam pass: schedule, parameter groups, AdamW, EMA (csrc/recipe.hip)
-    "rlt_recipe_chunk": (c_size_t, []),
-    "rlt_recipe_grid": (c_int, []),
-    "rlt_lr_at": (c_double, [P, c_int64]),
-    "rlt_adam_step_recipe": (c_int, [P, P, P, P, P, c_size_t, P, P, c_int, P, P, P, P]),
-    "rlt_swap_f32": (c_int, [P, P, c_size_t, P]),
-    # paired significance tests between per-query columns (csrc/compare.hip)
-    "rlt_paired_compare_plan": (c_int, [c_int, c_int, c_int, P]),
-    "rlt_paired_compare_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "rlt_paired_compare": (c_int, [P, P, c_int, c_int, c_int, c_int, c_uint32, P, c_size_t, P, P, P, P]),
-    # path-level entry points (one call per module forward / backward)
-    "rlt_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "rlt_encoder_layer_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_size_t, P, c_size_t, c_int, P]),
-    "rlt_encoder_layer_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_size_t, P, P, P, c_size_t, c_int, P]),
-    "rlt_bilstm_fwd": (c_int, [P, c_int, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
-    "rlt_bilstm_bwd": (c_int, [P, c_int, P, P, P, c_int, c_int, P, c_size_t, P, P, P, c_size_t, c_int, P]),
-    # sparse layer-0 input (BiCut on its bag-of-words input)
-    "rlt_sparse_inproj_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "rlt_sparse_inproj_fwd": (c_int, [P, c_int, c_int, P, P, P, P, P, P, P, P]),
-    "rlt_sparse_inproj_bwd": (c_int, [P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P]),
-    "rlt_bilstm_sparse_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "rlt_bilstm_sparse_fwd": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
-    "rlt_bilstm_sparse_bwd": (c_int, [P, P, P, P, c_int, c_int, P, c_size_t, P, P, c_size_t, c_int, P]),
-    "rlt_bilstm_generic_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "rlt_bilstm_generic_fwd": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P, c_size_t, c_int, P]),
-    "rlt_bilstm_generic_bwd": (c_int, [P, c_int, c_int, P, P, P, c_int, c_int, P, c_size_t, P, P, P, c_size_t, c_int, P]),
-}
-OP_ENCODER_STASH, OP_ENCODER_FWD_WS, OP_ENCODER_BWD_WS, OP_BILSTM_STASH, OP_BILSTM_WS = 1, 2, 3, 4, 5
+OP_ENCODER_STASH, OP_ENCODER_FWD_WS, OP_ENCODER_BWD_WS, OP_BILSTM_STASH, OP_BILSTM_WS = _rlt(
+    "OP", "ENCODER_STASH ENCODER_FWD_WS ENCODER_BWD_WS BILSTM_STASH BILSTM_WS")
 ENCODER_FIELDS = ("in_proj_weight", "in_proj_bias", "out_proj_weight", "out_proj_bias", "norm1_weight", "norm1_bias",
                   "linear1_weight", "linear1_bias", "linear2_weight", "linear2_bias", "norm2_weight", "norm2_bias")
 
@@ -188,7 +57,7 @@ class LstmLayerPtrs(ctypes.Structure):
     _fields_ = [("w_ih", c_void_p * 2), ("w_hh", c_void_p * 2), ("b_ih", c_void_p * 2), ("b_hh", c_void_p * 2)]
 
 
-SPARSE_CHUNK = 256          # RLT_SPARSE_CHUNK
+SPARSE_CHUNK = DEFINES["RLT_SPARSE_CHUNK"]
 SPARSE_POINTERS = ("dense", "ids", "perm", "indptr", "indices", "values", "col_ptr", "col_rows", "col_vals",
                    "chunk_col", "chunk_ptr", "multi_cols")
 SPARSE_INTS = ("Dn", "n_docs", "V", "n_chunks", "n_multi")
@@ -330,12 +199,13 @@ def lr_at(recipe, t):
 
 
 # the record of rlt_paired_compare: CMP_WORDS 8-byte words per system (RLT_CMP_*), the float64 ones through .view(torch.float64)
-CMP_WORDS = 16
 (CMP_N, CMP_SUM_BASE, CMP_SUM_SYS, CMP_SUM_D, CMP_SSD, CMP_WINS, CMP_TIES, CMP_LOSSES, CMP_NONFINITE, CMP_T_OBS, CMP_RAND_GE,
- CMP_BOOT_LE0, CMP_BOOT_GE0, CMP_RESAMPLES, CMP_FORM, CMP_RESERVED) = range(16)
+ CMP_BOOT_LE0, CMP_BOOT_GE0, CMP_RESAMPLES, CMP_FORM, CMP_RESERVED, CMP_WORDS) = _rlt(
+    "CMP", "N SUM_BASE SUM_SYS SUM_D SSD WINS TIES LOSSES NONFINITE T_OBS RAND_GE BOOT_LE0 BOOT_GE0 RESAMPLES FORM RESERVED WORDS")
 CMP_F64_WORDS = (CMP_SUM_BASE, CMP_SUM_SYS, CMP_SUM_D, CMP_SSD, CMP_T_OBS)
 CMP_FORMS = ("none", "resident", "chunked")                                         # RLT_COMPARE_RESIDENT, RLT_COMPARE_CHUNKED
-CMP_MAX_Q, CMP_MAX_SYSTEMS, CMP_MAX_R = 1 << 26, 8, 1 << 20
+CMP_MAX_Q, CMP_MAX_R = 1 << 26, 1 << 20                                             # limits the header states in words only
+CMP_MAX_SYSTEMS = DEFINES["RLT_COMPARE_MAX_SYSTEMS"]
 CMP_PLAN_FIELDS = ("form", "chunk", "resident_max_q", "chunks", "replicates_per_wave", "lds_bytes")
 
 
@@ -389,7 +259,6 @@ def byte_buffer(nbytes, device):
     """256-byte aligned device buffer of at least nbytes (torch's caching allocator aligns to 512)."""
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
-EXPORTS = tuple(_SIGNATURES)
 
 _lib = None
 
@@ -408,7 +277,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.rlt_abi_version() != 5:
+    if lib.rlt_abi_version() != ABI_VERSION:
         raise RuntimeError("librlt_hip.so ABI version mismatch")
     _lib = lib
     return lib

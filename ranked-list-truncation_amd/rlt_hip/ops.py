@@ -262,25 +262,43 @@ def add_layernorm(x, r, gamma, beta, eps=1e-5, drop_p=0.0):
 
 
 # ------------------------------------------------------------------------------ list-axis attention
+def _list_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr):
+    """-> (out (S*B, E), lse (S,H,B), the images the backward reads or None)."""
+    out = _empty((S * B, qkv.shape[1] // 3), qkv)
+    lse = _empty((S, H, B), qkv)
+    img_bytes = query("rlt_list_attention_fwd_workspace", S, B, H, HD, drop_p, pr)
+    images = workspace(img_bytes, qkv.device) if img_bytes else None     # pre-split tile records / images of this call
+    _launch("attn_fwd", lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, seed,
+                                     ptr(out), ptr(lse), ptr(images), img_bytes, pr, stream()))
+    # kept for the backward only where it reads them (split-bf16 records); the images of the pipelined bf16x6 forward kernels
+    # are scratch of the call above - several GB per layer at the benchmark sizes
+    if images is not None and not N.load().rlt_list_attention_images_retained(S, B, H, HD, pr):
+        images = None
+    return out, lse, images
+
+
+def _list_attention_bwd(qkv, out, dout, lse, images, S, B, H, HD, drop_p, seed, pr):
+    dqkv = torch.empty_like(qkv)
+    ws_bytes = query("rlt_list_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
+    ws = workspace(ws_bytes, qkv.device)
+    call("rlt_list_attention_bwd_prepare", ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, ptr(images), ptr(ws), ws_bytes, pr, stream())
+    _launch("attn_bwd_dkv", lambda: call("rlt_list_attention_bwd_dkv", ptr(qkv), ptr(dout), ptr(lse), ptr(images), ptr(ws), ws_bytes,
+                                         S, B, H, HD, drop_p, seed, ptr(dqkv), pr, stream()))
+    _launch("attn_bwd_dq", lambda: call("rlt_list_attention_bwd_dq", ptr(qkv), ptr(dout), ptr(lse), ptr(images), ptr(ws), ws_bytes,
+                                        S, B, H, HD, drop_p, seed, ptr(dqkv), pr, stream()))
+    return dqkv
+
+
 class ListAttentionFn(Function):
     """qkv (S*B, 3E) -> concatenated heads (S*B, E); attention over the B lists at each position."""
 
     @staticmethod
     def forward(ctx, qkv, S, B, H, drop_p=0.0, seed=0):
-        E = qkv.shape[1] // 3
-        HD = E // H
-        out = _empty((S * B, E), qkv)
-        lse = _empty((S, H, B), qkv)
+        HD = qkv.shape[1] // 3 // H
         ctx.prec = pr = current_precision()
-        img_bytes = query("rlt_list_attention_fwd_workspace", S, B, H, HD, drop_p, pr)
-        images = workspace(img_bytes, qkv.device) if img_bytes else None     # pre-split tile records / images of this call
-        _launch("attn_fwd", lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, seed,
-                                         ptr(out), ptr(lse), ptr(images), img_bytes, pr, stream()))
+        out, lse, ctx.images = _list_attention_fwd(qkv, S, B, H, HD, drop_p, seed, pr)
         ctx.dims = (S, B, H, HD)
         ctx.drop = (drop_p, seed)
-        # kept for the backward only where it reads them (split-bf16 records); the images of the pipelined bf16x6 forward kernels
-        # are scratch of the call above - several GB per layer at the benchmark sizes
-        ctx.images = images if images is not None and N.load().rlt_list_attention_images_retained(S, B, H, HD, pr) else None
         ctx.save_for_backward(qkv, out, lse)
         return out
 
@@ -288,18 +306,8 @@ class ListAttentionFn(Function):
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
         S, B, H, HD = ctx.dims
-        images = ctx.images
-        dout = N.f32c(dout)
-        dqkv = torch.empty_like(qkv)
-        pr = ctx.prec
         drop_p, seed = ctx.drop
-        ws_bytes = query("rlt_list_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
-        ws = workspace(ws_bytes, qkv.device)
-        call("rlt_list_attention_bwd_prepare", ptr(out), ptr(dout), ptr(lse), S, B, H, HD, drop_p, ptr(images), ptr(ws), ws_bytes, pr, stream())
-        _launch("attn_bwd_dkv", lambda: call("rlt_list_attention_bwd_dkv", ptr(qkv), ptr(dout), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                             S, B, H, HD, drop_p, seed, ptr(dqkv), pr, stream()))
-        _launch("attn_bwd_dq", lambda: call("rlt_list_attention_bwd_dq", ptr(qkv), ptr(dout), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                            S, B, H, HD, drop_p, seed, ptr(dqkv), pr, stream()))
+        dqkv = _list_attention_bwd(qkv, out, N.f32c(dout), lse, ctx.images, S, B, H, HD, drop_p, seed, ctx.prec)
         ctx.images = None
         return dqkv, None, None, None, None, None
 
@@ -509,14 +517,7 @@ class EncoderLayerKernelsFn(Function):
         if ctx.axis == "position":
             att, lse = _seq_attention_fwd(qkv, S, B, H, HD, drop_p, s_attn, pr, ctx.causal)
         else:
-            att = _empty((T, E), x)
-            lse = _empty((S, H, B), x)
-            img_bytes = query("rlt_list_attention_fwd_workspace", S, B, H, HD, drop_p, pr)
-            images = workspace(img_bytes, x.device) if img_bytes else None
-            _launch("attn_fwd", lambda: call("rlt_list_attention_fwd", ptr(qkv), S, B, H, HD, drop_p, s_attn,
-                                             ptr(att), ptr(lse), ptr(images), img_bytes, pr, stream()))
-            if images is not None and not N.load().rlt_list_attention_images_retained(S, B, H, HD, pr):
-                images = None                                    # scratch of the forward call: not kept for the backward
+            att, lse, images = _list_attention_fwd(qkv, S, B, H, HD, drop_p, s_attn, pr)
         proj = _empty((T, E), x)
         gemm(0, 1, T, E, E, att, E, out_w, E, proj, E, bias=out_b)
         h1 = _empty((T, E), x)
@@ -586,15 +587,7 @@ class EncoderLayerKernelsFn(Function):
         if ctx.axis == "position":
             dqkv = _seq_attention_bwd(qkv, att, datt, lse, S, B, H, HD, drop_p, s_attn, pr, ctx.causal)
         else:
-            images = ctx.images
-            dqkv = torch.empty_like(qkv)
-            ws_bytes = query("rlt_list_attention_bwd_workspace", S, B, H, HD, drop_p, pr)
-            ws = workspace(ws_bytes, x.device)
-            call("rlt_list_attention_bwd_prepare", ptr(att), ptr(datt), ptr(lse), S, B, H, HD, drop_p, ptr(images), ptr(ws), ws_bytes, pr, stream())
-            _launch("attn_bwd_dkv", lambda: call("rlt_list_attention_bwd_dkv", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                                 S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
-            _launch("attn_bwd_dq", lambda: call("rlt_list_attention_bwd_dq", ptr(qkv), ptr(datt), ptr(lse), ptr(images), ptr(ws), ws_bytes,
-                                                S, B, H, HD, drop_p, s_attn, ptr(dqkv), pr, stream()))
+            dqkv = _list_attention_bwd(qkv, att, datt, lse, ctx.images, S, B, H, HD, drop_p, s_attn, pr)
             ctx.images = None
         # in_proj
         dw_in, db_in = _empty((3 * E, E), x), _empty((3 * E,), x)

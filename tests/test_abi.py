@@ -18,6 +18,7 @@ def native():
 
 
 def test_header_symbols_are_exported_and_bound(native):
+    """The names a plain regex finds in the raw header are exactly the bound set; the other test_*_abi.py files check their own names."""
     header = open(os.path.join(REPO, "include", "rlt_hip.h")).read()
     declared = set(re.findall(r"\b(rlt_[a-z0-9_]+)\s*\(", header))
     assert declared, "no declarations found"
