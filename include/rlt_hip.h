@@ -1044,6 +1044,48 @@ int rlt_hazard_head_append(const float* x, const float* w, const float* b, const
                            int final, double* carry, double tau, int32_t* active, int32_t* k, float* stop, float* p, float* z,
                            void* stream);
 
+/* ------------------------------------------------------------------ streaming: compacting the live lists
+ * A retired list still occupies a slot of the batch: the two append calls above skip it, the chunk's GEMMs and LayerNorms do not,
+ * and what the attention skips is one cache row in every B.  These two calls take the retired slots OUT of a running stream
+ * (csrc/stream_compact.hip; inference only).  tests: tests/test_stream_compact_abi.py, tests/test_stream_compact_gpu.py against the
+ * numpy restatement tests/stream_compact_restate.py; utils/stream.py drives them (tests/test_stream_compact_model_gpu.py).
+ * rlt_stream_compact_plan: the slot map and the per-list state.  B: the slots of the stream as it stands; B_full: the lists the
+ * stream started with.  All arrays are device memory.
+ *   active (B) int32, required: a slot is LIVE iff active[b] != 0 (any non-zero value).  origin (B) int32: the original list number
+ *   of each slot, or NULL for the identity.  carry (B) float64 with carry_out (B), or both NULL.  k (B) int32 with k_full (B_full),
+ *   or both NULL.
+ *   slot_src (B): entries 0 .. n_live-1 are the live slots in ASCENDING order (a stable partition); the entries behind are -1.
+ *   origin_out (B): origin[slot_src[j]] for j < n_live, -1 behind.  carry_out[j] = carry[slot_src[j]] for j < n_live, copied
+ *   bitwise (NaN payloads, -0.0); its entries >= n_live are UNTOUCHED.  k_full[origin[b]] = k[b] for every slot with
+ *   active[b] == 0: a retired list hands its cut over before its slot disappears; an origin value outside [0, B_full) is skipped,
+ *   not written, and the entries of k_full that belong to live or absent lists are UNTOUCHED.  n_live (1): an int32 in device
+ *   memory - the host is not synchronised; the caller reads it back when it wants to size the next launches.
+ *   One workgroup walks B in chunks of 1024 with ballot / popcount prefixes and a carried count: no atomics, one fixed order, two
+ *   calls give the same bits; no allocation.  Made for a B of a few thousand (time at B = 8192 and 1,048,576: DESIGN.md); not tuned.
+ *   Errors before any launch, in this order: RLT_E_ARG (active, slot_src, origin_out or n_live NULL; one half of a pair without
+ *   the other; B or B_full not positive; B > B_full; an output pointer equal to an input pointer or to another output pointer),
+ *   RLT_E_SHAPE (the index limit: B_full > 2^30), RLT_E_ALIGN (carry / carry_out off 8 bytes, an int array off 4).
+ *   Algorithmic bytes: reads 4 B (+ 4 B origin, 8 B carry, 4 B k), writes 8 B (+ 8 n_live, 4 (B - n_live)) + 4.
+ * rlt_kv_cache_compact: the K/V cache of one layer, gathered through the map.
+ *   src (t0*B_src, W) position-major: the first t0 ranks of a cache of B_src slots, W = 2E floats a row.  dst (t0*B_dst, W).
+ *   dst[(s*B_dst + j)*W ..] = src[(s*B_src + slot_src[j])*W ..] for s < t0, j < B_dst, copied bitwise (NaN payloads and signed
+ *   zeros survive).  Rows of dst at or behind t0*B_dst are neither read nor written; src is not written.  A slot_src[j] outside
+ *   [0, B_src) leaves row j of every rank UNTOUCHED: the kernel bounds what it reads by construction - it cannot validate device
+ *   data without a synchronising copy.  The ranges [src, src + t0*B_src*W) and [dst, dst + t0*B_dst*W) must not overlap (checked
+ *   on the host from the pointer values): there is no in-place form, it would race between workgroups.  t0 == 0 or B_dst == 0
+ *   returns 0 without a launch (after the checks).  After the call dst is a cache of B_dst slots for rlt_seq_attention_append at
+ *   the same t0: the append's arithmetic for a list does not depend on B or on the list's slot, so the stream continues bit for bit.
+ *   An HBM-bound gather copy: 16-byte loads and stores, four rows in flight per lane group before the first store, the grid strided
+ *   over (rank, destination slot), the map entry read once per row.  No atomics, no allocation, no host synchronisation.
+ *   Errors before any launch, in this order: RLT_E_ARG (src, dst or slot_src NULL; t0 < 0; B_src < 1; B_dst < 0; B_dst > B_src;
+ *   W < 1; overlap), RLT_E_SHAPE (W % 4 != 0; W > 2048; the index limits: t0*B_src*W >= 2^40 elements, B_src > 2^30),
+ *   RLT_E_ALIGN (src or dst off 16 bytes).
+ *   Algorithmic bytes: reads 4*t0*B_dst*W (+ 4*B_dst of the map), writes 4*t0*B_dst*W. */
+int rlt_stream_compact_plan(const int32_t* active, const int32_t* origin, const double* carry, const int32_t* k, int B, int B_full,
+                            int32_t* slot_src, int32_t* origin_out, double* carry_out, int32_t* k_full, int32_t* n_live,
+                            void* stream);
+int rlt_kv_cache_compact(const float* src, float* dst, const int32_t* slot_src, int t0, int B_src, int B_dst, int W, void* stream);
+
 /* ------------------------------------------------------------------ probe heads (the probing study)
  * models/Classification.py:4-12 (TaskC), models/Rerank.py:4-12 (TaskR), models/Probe.py:30-53,102-122 (TowerClass /
  * TowerRerank as the six probes of Probe), with their training losses of verify_BMT.py:37-44,71-80 and

@@ -29,14 +29,16 @@ class Choopy(C.CutModel):
         h = C.encoder(h, self.attention_layer, self.n_head, S, B, drop_p, self.attention_axis, self.attention_mask == "causal")
         return C.cut_head(self, h, S, B)
 
-    def stream(self, tau, batch_size):
+    def stream(self, tau, batch_size, compact_every=None, compact_below=1.0):
         """-> utils.stream.StreamingTruncator: the model fed a page of ranks at a time, stopping each list on the device at the
         first rank whose stop probability reaches tau (what truncate(rule='above', tau=tau) gives on the whole list).  Needs
-        attention_axis='position', attention_mask='causal' and cut_head='hazard': anything else is a ValueError naming the option."""
+        attention_axis='position', attention_mask='causal' and cut_head='hazard': anything else is a ValueError naming the option.
+        compact_every=n takes the stopped lists out of the batch after every n-th page (None: never), compact_below is the live
+        fraction at or below which that moves anything (StreamingTruncator.compact)."""
         for name, want, why in (("attention_axis", "position", "the list axis attends across the lists of a batch, not over ranks"),
                                 ("attention_mask", "causal", "without the mask rank i attends to the ranks below it"),
                                 ("cut_head", "hazard", "the softmax head normalises over the whole list")):
             if getattr(self, name) != want:
                 raise ValueError(f"Choopy.stream needs {name}={want!r}, this model has {name}={getattr(self, name)!r}: {why}")
         from utils.stream import StreamingTruncator
-        return StreamingTruncator(self, tau, batch_size)
+        return StreamingTruncator(self, tau, batch_size, compact_every=compact_every, compact_below=compact_below)

@@ -213,7 +213,7 @@ class CutModel(nn.Module):
                   "MtChoopy": "its multi-task heads (softmax re-ranking, classification) normalise over the whole list",
                   "BiCut": "its BiLSTM runs over the list in both directions"}
 
-    def stream(self, tau, batch_size):
+    def stream(self, tau, batch_size, compact_every=None, compact_below=1.0):
         """Only a Choopy with attention_axis='position', attention_mask='causal', cut_head='hazard' can truncate online
         (utils/stream.py); every other model raises ValueError saying why."""
         why = self._NO_STREAM.get(type(self).__name__, "its output at a rank is not computed from the ranks above it alone")

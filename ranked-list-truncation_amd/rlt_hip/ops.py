@@ -1055,6 +1055,64 @@ def hazard_head_append(x_pm, weight, bias, t0, B, carry, tau=1.0, final=False, a
     return {"stop": stop, "p": p, "z": z}
 
 
+def _check_slots(t, n, dtype, like, what, name):
+    if t.dtype != dtype or t.shape != (n,) or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{what}: {name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape ({n},) on {like.device}")
+
+
+def stream_compact_plan(active, origin=None, carry=None, k=None, k_full=None):
+    """Streaming (inference only): the slot map that takes the retired lists out of a running stream (rlt_stream_compact_plan).
+    active (B,) int32: a slot is live iff non-zero; origin (B,) int32: each slot's original list number, None = the identity; carry
+    (B,) float64 or None; k (B,) int32 together with k_full (B_full,) int32, written in place - k_full[origin[b]] = k[b] for every
+    retired slot -, or neither.  -> {'slot_src': (B,) int32, the live slots ascending then -1, 'origin': (B,) int32, their original
+    numbers then -1, 'carry': (B,) float64 gathered through slot_src (None without carry; not initialised behind the live slots),
+    'n_live': (1,) int32 ON THE DEVICE: the call does not synchronise}."""
+    N.require_cuda(active)
+    if active.dim() != 1 or active.shape[0] < 1:
+        raise ValueError(f"stream_compact_plan: active must be a contiguous int32 tensor of shape (B,) with B >= 1, got {tuple(active.shape)}")
+    B = int(active.shape[0])
+    _check_active(active, B, active, "stream_compact_plan")
+    if origin is not None:
+        _check_slots(origin, B, torch.int32, active, "stream_compact_plan", "origin")
+    if carry is not None:
+        _check_slots(carry, B, torch.float64, active, "stream_compact_plan", "carry")
+    if (k is None) != (k_full is None):
+        raise ValueError("stream_compact_plan: pass both `k` and `k_full`, or neither")
+    B_full = B
+    if k is not None:
+        _check_slots(k, B, torch.int32, active, "stream_compact_plan", "k")
+        if k_full.dim() != 1 or k_full.shape[0] < B:
+            raise ValueError(f"stream_compact_plan: k_full must be a contiguous int32 tensor of shape (B_full,) with B_full >= B = {B}, got {tuple(k_full.shape)}")
+        B_full = int(k_full.shape[0])
+        _check_slots(k_full, B_full, torch.int32, active, "stream_compact_plan", "k_full")
+        if k_full.data_ptr() == k.data_ptr():
+            raise ValueError("stream_compact_plan: k_full must not be k itself (the call reads one while it writes the other)")
+    slot_src, origin_out = torch.empty_like(active), torch.empty_like(active)
+    carry_out = None if carry is None else torch.empty_like(carry)
+    n_live = torch.empty(1, dtype=torch.int32, device=active.device)
+    _launch("stream_compact_plan", lambda: call("rlt_stream_compact_plan", ptr(active), ptr(origin), ptr(carry), ptr(k), B, B_full, ptr(slot_src),
+                                                ptr(origin_out), ptr(carry_out), ptr(k_full), ptr(n_live), stream()))
+    return {"slot_src": slot_src, "origin": origin_out, "carry": carry_out, "n_live": n_live}
+
+
+def kv_cache_compact(src, dst, slot_src, t0, B_src, B_dst):
+    """Streaming (inference only): gather the first t0 ranks of a K/V cache of B_src slots into one of B_dst slots through the map
+    of stream_compact_plan (rlt_kv_cache_compact): dst row s*B_dst + j = src row s*B_src + slot_src[j], bit for bit.  src
+    (>= t0*B_src, 2E) and dst (>= t0*B_dst, 2E) fp32, contiguous, two different buffers; slot_src int32 with at least B_dst entries.
+    dst is written in place; its rows from t0*B_dst on are not touched."""
+    N.require_cuda(src)
+    if min(t0, B_dst) < 0 or B_src < 1 or B_dst > B_src:
+        raise ValueError(f"kv_cache_compact: t0 = {t0}, B_src = {B_src}, B_dst = {B_dst} is not a compaction of t0 >= 0 ranks to 0 <= B_dst <= B_src slots")
+    for t, rows, name in ((src, t0 * B_src, "src"), (dst, t0 * B_dst, "dst")):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[0] < rows or t.device != src.device:
+            raise ValueError(f"kv_cache_compact: {name} must be a contiguous fp32 tensor of at least {rows} rows on {src.device}, got {tuple(t.shape)}")
+    if src.shape[1] != dst.shape[1]:
+        raise ValueError(f"kv_cache_compact: src and dst rows differ, {src.shape[1]} and {dst.shape[1]} columns")
+    if slot_src.dtype != torch.int32 or slot_src.dim() != 1 or not slot_src.is_contiguous() or slot_src.shape[0] < B_dst or slot_src.device != src.device:
+        raise ValueError(f"kv_cache_compact: slot_src must be a contiguous int32 tensor of at least {B_dst} entries on {src.device}")
+    _launch("kv_cache_compact", lambda: call("rlt_kv_cache_compact", ptr(src), ptr(dst), ptr(slot_src), t0, B_src, B_dst, int(src.shape[1]), stream()))
+
+
 # ------------------------------------------------------------------------------ MMOE
 class MMOEGateFn(Function):
     """gates (n_tasks,B,n_e) = softmax_e(flatten_s(h[b]) @ w_gate[t])."""

@@ -670,17 +670,19 @@ class Trainer:
                 np.savez(out_path, summary=np.asarray(json.dumps(results)), lengths=np.asarray(sorted(map(int, results))), **arrays)
         return results
 
-    def stream_eval(self, page, tau):
+    def stream_eval(self, page, tau, compact=0, compact_below=1.0):
         """--stream-eval: the test split once more, a page of `page` ranks at a time through model.stream; the lists of a
         bucket whose length is not the model's seq_len cannot be streamed and are an error.  Means over the lists: the streamed
         cut, F1 and DCG at it (ops.cut_metrics with k_in) and the ranks read (whole pages up to the stop).  No collective: rank
-        0 calls it.  One host read per batch, after its last page."""
-        n, tot = 0, [0.0, 0.0, 0.0, 0.0]
+        0 calls it.  One host read per batch, after its last page.  compact (--stream-compact N): the stopped lists leave the batch
+        after every N-th page (one 4-byte read more per compaction); then also the mean rows computed per list, beside the
+        seq_len rounded up to pages that every list costs without it."""
+        n, tot, rows = 0, [0.0, 0.0, 0.0, 0.0], 0
         for X, y in self.test_loader:
             B, S = int(X.shape[0]), int(X.shape[1])
             if S != self.model.seq_len:
                 raise ValueError(f"--stream-eval: a test bucket of length {S} does not match the model's seq_len {self.model.seq_len}")
-            st = self.model.stream(tau, B)
+            st = self.model.stream(tau, B, compact_every=compact or None, compact_below=compact_below)
             scores = X.to(self.device, non_blocking=True)[..., :1].contiguous()
             for t0 in range(0, S, page):
                 st.push(scores[:, t0:t0 + page].contiguous())
@@ -689,10 +691,16 @@ class Trainer:
             vals = torch.stack([k.double().sum(), f1.sum(), dcg.sum(), st.documents_read().double().sum()]).tolist()
             tot = [a + b for a, b in zip(tot, vals)]
             n += B
+            rows += st.rows_computed()
         res = {"stream_page": int(page), "stream_tau": float(tau), "stream_lists": n, "stream_k": tot[0] / n, "stream_f1": tot[1] / n,
                "stream_dcg": tot[2] / n, "stream_read": tot[3] / n}
         logging.info('\tStreamed test (pages of {}, tau = {}): cut = {:.3f} | f1 = {:.6f} | dcg = {:.6f} | ranks read = {:.3f}\n'.format(
             page, tau, res["stream_k"], res["stream_f1"], res["stream_dcg"], res["stream_read"]))
+        if compact:
+            res.update(stream_compact=int(compact), stream_compact_below=float(compact_below), stream_rows=rows / n,
+                       stream_rows_full=float((self.model.seq_len + page - 1) // page * page))
+            logging.info('\tCompacted every {} pages (live fraction <= {}): rows computed per list = {:.3f} of {:.0f}\n'.format(
+                compact, compact_below, res["stream_rows"], res["stream_rows_full"]))
         return res
 
     def draw(self, epoch):
@@ -732,7 +740,8 @@ class Trainer:
             if getattr(self.args, "cut_sweep", None) and self.rank == 0:
                 self.sweep_results = self.cut_sweep(self.args.cut_sweep, getattr(self.args, "sweep_out", None))
             if getattr(self.args, "stream_eval", 0) and self.rank == 0:
-                self.stream_results = self.stream_eval(self.args.stream_eval, getattr(self.args, "stream_tau", 0.5))
+                self.stream_results = self.stream_eval(self.args.stream_eval, getattr(self.args, "stream_tau", 0.5),
+                                                          getattr(self.args, "stream_compact", 0), getattr(self.args, "stream_compact_below", 1.0))
         top = sorted(self.f1_record, reverse=True)[:5]
         topd = sorted(self.dcg_record, reverse=True)[:5]
         best5_f1, best5_dcg = sum(top) / 5, sum(topd) / 5       # run.py:229-230 divides by 5 regardless
@@ -867,6 +876,12 @@ def build_parser():
                         "walk the test split in pages of C ranks through model.stream (utils/stream.py) and log the mean cut, F1 and "
                         "DCG at the streamed cut and the mean ranks read; `stream_*` keys in --history-json.  0 = off")
     p.add_argument('--stream-tau', type=float, default=0.5, help="the stop threshold of --stream-eval (truncate's rule 'above')")
+    p.add_argument('--stream-compact', type=int, default=0, metavar='N',
+                   help="with --stream-eval: take the stopped lists out of the batch after every N-th page (StreamingTruncator.compact), so "
+                        "that the pages behind a stop cost no GEMM rows; `stream_compact`, `stream_rows`, `stream_rows_full` in "
+                        "--history-json.  0 = off")
+    p.add_argument('--stream-compact-below', type=float, default=1.0, metavar='F',
+                   help="--stream-compact moves the caches only when at most this fraction of the batch's slots is still live")
     p.add_argument('--history-json', type=str, default=None, help="rank 0 writes the per-epoch train / test means and the best / best-5 figures here")
     p.add_argument('--param-dump-dir', type=str, default=None,
                    help="every rank saves its final flat parameter bucket as flat_param_rank<r>.npy here (data-parallel checks: the "
@@ -964,6 +979,10 @@ def main(argv=None):
                                  and args.cut_head == "hazard"):
         parser.error("--stream-eval needs --model-name choopy --attention-axis position --attention-mask causal --cut-head hazard "
                      "(only that model computes rank i from the ranks above it)")
+    if args.stream_compact < 0 or not 0.0 <= args.stream_compact_below <= 1.0:
+        parser.error("--stream-compact takes a positive number of pages (0 = off), --stream-compact-below a fraction in [0, 1]")
+    if args.stream_compact and not args.stream_eval:
+        parser.error("--stream-compact needs --stream-eval (it compacts the batch of the streamed test pass)")
     if args.attention_mask == "causal" and args.attention_axis != "position":
         parser.error("--attention-mask causal needs --attention-axis position (the list axis attends across lists, not positions)")
     # RLT_FORCE_DIST=1: initialise the process group (and run the step's collectives) even with one rank - the RCCL

@@ -1751,8 +1751,133 @@ def stream_bench(reps=7, runs=2, S=300, pages=(1, 10, 32)):
         print(f"stream choopy B{B} S{S} E128 H8 L3 run {r} page 10, every other list retired at rank 30: {s:9.3f} ms", flush=True)
 
 
+def stream_compact_bench(reps=7, runs=2, S=300, pages=(10, 32)):
+    """Streaming truncation with batch compaction (rlt_stream_compact_plan, rlt_kv_cache_compact, StreamingTruncator.compact): the
+    shapes and the method of `stream` - medians of `reps` HIP-event timings in each of `runs` runs.
+      1. the whole model (Choopy, 8192 lists, E 128, 8 heads, 3 layers): the time to stream 300 ranks with compact_every None, 1, and
+         3 with compact_below 0.5, under four retirement schedules forced through `active`: none; every other list at rank 30; the
+         second half of the lists at rank 30; geometric - half of the live lists every 30 ranks.  Beside each time the rows the GEMMs
+         ran over, as a fraction of 300 * 8192.
+      2. the attention alone (4096 lists, 4 heads of 64): the append kernel at C = 1, t0 = 299 on the full batch, on the batch with
+         lists retired through `active`, and on the compacted cache; and the streamed attention at page 10.
+      3. the gather kernel alone, as GB/s on its 2 * 4 * t0 * B_dst * W bytes (the float4-copy yardstick is tools/micro/membw, run in
+         the same job), and the plan launch at B = 8192 and 1,048,576."""
+    import models as hm
+    from rlt_hip import ops
+    D = N.PRECISION_DEFAULT
+    i32 = lambda *a, **k: torch.zeros(*a, dtype=torch.int32, device=dev, **k)
+
+    def retire(active, how):
+        """clear entries of a slot array on the device, no host read: 'alternate' every second LIVE slot, 'upper' the second half of them"""
+        live = active != 0
+        cs = torch.cumsum(live.int(), 0)
+        gone = (cs % 2 == 0) if how == "alternate" else (2 * cs > cs[-1])
+        active[gone & live] = 0
+
+    # ---- 3. the two kernels alone
+    for B, Bd, W, t0s in ((8192, 4096, 256, (150, 299)), (4096, 2048, 512, (150, 299))):
+        src, dst = torch.randn(S * B, W, device=dev), torch.empty(S * Bd, W, device=dev)
+        for what in ("alternate", "upper"):
+            act = torch.ones(B, dtype=torch.int32, device=dev)
+            retire(act, what)
+            plan = ops.stream_compact_plan(act)
+            assert int(plan["n_live"].item()) == Bd
+            for t0 in t0s:
+                for r in range(runs):
+                    t = _seq_median_ms(lambda: call("rlt_kv_cache_compact", ptr(src), ptr(dst), ptr(plan["slot_src"]), t0, B, Bd, W, stream()), reps)
+                    print(f"stream_compact gather {B} -> {Bd} lists ({'every other list' if what == 'alternate' else 'the first half'} live) W{W} "
+                          f"t0 {t0} run {r}: {t * 1e3:9.1f} us  {2 * 4 * t0 * Bd * W / t / 1e6:8.1f} GB/s on 2*4*t0*B_dst*W", flush=True)
+        del src, dst
+    torch.cuda.empty_cache()
+    for B in (8192, 1 << 20):
+        act = (torch.arange(B, device=dev) % 3 != 0).int()
+        org, car, k, kf = torch.arange(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.float64, device=dev), i32(B), i32(B)
+        outs = [i32(B), i32(B), torch.empty(B, dtype=torch.float64, device=dev), i32(1)]
+        f = lambda: call("rlt_stream_compact_plan", ptr(act), ptr(org), ptr(car), ptr(k), B, B, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(kf),
+                         ptr(outs[3]), stream())
+        for r in range(runs):
+            print(f"stream_compact plan B {B} (origin, carry and k given) run {r}: {_seq_median_ms(f, reps) * 1e3:9.1f} us", flush=True)
+    # ---- 2. the attention alone
+    B, H, HD = 4096, 4, 64
+    E = H * HD
+    qkv = torch.randn(S * B, 3 * E, device=dev)
+    out = torch.empty(S * B, E, device=dev)
+    cache, cache2 = torch.randn(S * B, 2 * E, device=dev), torch.empty(S * B, 2 * E, device=dev)
+
+    def append(t0, c, cch, Bs, active=None):
+        call("rlt_seq_attention_append", N.c_void_p(qkv.data_ptr() + 4 * t0 * Bs * 3 * E), ptr(cch), t0, c, S, Bs, H, HD, ptr(active),
+             N.c_void_p(out.data_ptr() + 4 * t0 * Bs * E), None, D, stream())
+
+    def attn_stream(c, how, compact):
+        act, cch, oth, Bs = torch.ones(B, dtype=torch.int32, device=dev), cache, cache2, B
+        for t0 in range(0, S, c):
+            if how and t0 and t0 % 30 == 0 and (how == "geometric" or t0 == 30):
+                retire(act, "alternate" if how != "upper" else "upper")
+                if compact:
+                    plan = ops.stream_compact_plan(act)
+                    n = int(plan["n_live"].item())
+                    if n:
+                        call("rlt_kv_cache_compact", ptr(cch), ptr(oth), ptr(plan["slot_src"]), t0, Bs, n, 2 * E, stream())
+                    cch, oth, Bs, act = oth, cch, n, torch.ones(n, dtype=torch.int32, device=dev)
+            if Bs:
+                append(t0, min(c, S - t0), cch, Bs, act)
+
+    for r in range(runs):
+        t = _seq_median_ms(lambda: append(S - 1, 1, cache, B), reps)
+        print(f"stream_compact attention B{B} S{S} H{H} HD{HD} run {r} append alone C 1 t0 {S - 1}, full batch: {t * 1e3:9.1f} us", flush=True)
+        for how, label in (("alternate", "every other list retired"), ("upper", "the second half of the lists retired")):
+            act = torch.ones(B, dtype=torch.int32, device=dev)
+            retire(act, how)
+            plan = ops.stream_compact_plan(act)
+            n = int(plan["n_live"].item())
+            call("rlt_kv_cache_compact", ptr(cache), ptr(cache2), ptr(plan["slot_src"]), S - 1, B, n, 2 * E, stream())
+            t_act = _seq_median_ms(lambda: append(S - 1, 1, cache, B, act), reps)
+            t_cmp = _seq_median_ms(lambda: append(S - 1, 1, cache2, n), reps)
+            print(f"stream_compact attention B{B} S{S} H{H} HD{HD} run {r} append alone C 1 t0 {S - 1}, {label}: through `active` {t_act * 1e3:9.1f} us | "
+                  f"compacted to {n} lists {t_cmp * 1e3:9.1f} us  {8 * (S - 1) * n * E / t_cmp / 1e6:8.1f} GB/s on 8 t B_live E", flush=True)
+        for how in ("alternate", "upper", "geometric"):
+            a, b = _seq_median_ms(lambda: attn_stream(10, how, False), reps), _seq_median_ms(lambda: attn_stream(10, how, True), reps)
+            print(f"stream_compact attention B{B} S{S} H{H} HD{HD} run {r} page 10, {how} from rank 30: through `active` {a:9.3f} ms | compacted {b:9.3f} ms "
+                  f"(plan, read and gather included) = {b / a:5.3f} x" + ("  (compaction is SLOWER here)" if b > a else ""), flush=True)
+    del qkv, out, cache, cache2
+    torch.cuda.empty_cache()
+    # ---- 1. the whole model
+    B = 8192
+    torch.manual_seed(3)
+    m = hm.Choopy(seq_len=S, d_model=128, n_head=8, num_layers=3, dropout=0.0, attention_axis="position", attention_mask="causal",
+                  cut_head="hazard").to(dev).eval()
+    x = torch.randn(B, S, 1, device=dev)
+    chunks = {c: [x[:, t0:t0 + c].contiguous() for t0 in range(0, S, c)] for c in pages}
+    modes = (("compact_every None", {}), ("compact_every 1", {"compact_every": 1}), ("compact_every 3, compact_below 0.5", {"compact_every": 3, "compact_below": 0.5}))
+    trunc = {name: m.stream(2.0, B, **kw) for name, kw in modes}          # tau = 2: nothing stops by itself
+
+    def model_stream(st, c, how):
+        st.reset()
+        nxt = 30
+        for page in chunks[c]:
+            if how and st.position >= nxt and st.slots:                    # the first page boundary at or behind rank 30, 60, ..
+                retire(st.active, "upper" if how == "upper" else "alternate")
+                nxt = nxt + 30 if how == "geometric" else S + 1
+            st.push(page)
+
+    for r in range(runs):
+        for c in pages:
+            for how, label in ((None, "no list retired"), ("alternate", "every other list retired at rank 30"),
+                               ("upper", "the second half of the lists retired at rank 30"), ("geometric", "half of the live lists retired every 30 ranks")):
+                base = None
+                for name, _ in modes:
+                    st = trunc[name]
+                    t = _seq_median_ms(lambda: model_stream(st, c, how), reps)
+                    base = t if base is None else base
+                    extra = f" = {t / base:5.3f} x compact_every None" + ("  (compaction is SLOWER here)" if t > base else "") if name != modes[0][0] else ""
+                    if how is None and name != modes[0][0]:
+                        extra += f", {(t - base) * 1e3 / len(chunks[c]):7.1f} us per push"
+                    print(f"stream_compact choopy B{B} S{S} E128 H8 L3 run {r} page {c:2d}, {label}, {name}: {t:9.3f} ms, GEMM rows "
+                          f"{st.rows_computed() / (S * B):5.3f} of S*B{extra}", flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["attention", "gemms", "lstm"]
     print("env:", {k: v for k, v in os.environ.items() if k.startswith("RLT_")}, flush=True)
     for w in which:
-        {"stream": stream_bench}.get(w, globals()[w])()          # (`stream` itself is the library's stream getter)
+        ({"stream": stream_bench, "stream_compact": stream_compact_bench}.get(w) or globals()[w])()          # (`stream` itself is the library's stream getter)

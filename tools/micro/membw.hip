@@ -32,6 +32,18 @@ __global__ __launch_bounds__(256) void rd(const float4* __restrict__ buf, size_t
     if (acc.x + acc.y + acc.z + acc.w == 12345.678f) sink[0] = acc.x;
 }
 
+// float4 copy: dst[i] = src[i], a grid-stride loop with four 16-byte loads in flight per lane (the yardstick of the HBM-bound copy
+// and gather kernels: bytes moved = 2 x the bytes copied)
+__global__ __launch_bounds__(256) void cp(const float4* __restrict__ src, float4* __restrict__ dst, size_t n4) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const float4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
+        dst[i] = a; dst[i + stride] = b; dst[i + 2 * stride] = c; dst[i + 3 * stride] = d;
+    }
+    for (; i < n4; i += stride) dst[i] = src[i];
+}
+
 int main() {
     const size_t npanel = 9600;                 // 9600 x 128 KB = 1.26 GB (the A matrix of the FFN GEMM)
     float4* buf; float* sink;
@@ -52,5 +64,16 @@ int main() {
                 const double gb = (double)grid * 128 * 1024 / 1e9;
                 printf("pattern %d share %2d remap %d: %8.3f ms  %7.2f TB/s (%.1f GB moved)\n", pattern, share, remap, ms, gb / ms, gb);
             }
+    for (size_t mb : {157, 629}) {                 // the copied bytes: near one half-compacted K/V cache, and the whole buffer's half
+        const size_t n4 = mb * 1000 * 1000 / 16;
+        float ms = 0;
+        for (int rep = 0; rep < 3; ++rep) {
+            CK(hipEventRecord(a));
+            hipLaunchKernelGGL(cp, dim3(2048), dim3(256), 0, 0, buf, buf + npanel * 128 * 1024 / 32, n4);
+            CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
+            CK(hipEventElapsedTime(&ms, a, b));
+        }
+        printf("float4 copy of %zu MB: %8.3f ms  %7.2f TB/s on 2 x the bytes copied\n", mb, ms, 2.0 * n4 * 16 / 1e9 / ms);
+    }
     return 0;
 }
