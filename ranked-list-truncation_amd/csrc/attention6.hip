@@ -1,5 +1,5 @@
 // List-axis attention, fp32-FAITHFUL variant on the bf16 matrix pipe ("bf16x6", the attention half of that mode; the GEMM
-// half is gemm6_kernel in gemm.hip): same algorithm, same interface and the same fp32 softmax arithmetic as the exact-fp32
+// half is gemm6_kernel in gemm6.hip): same algorithm, same interface and the same fp32 softmax arithmetic as the exact-fp32
 // kernels of attention.hip, but every MFMA product a*b is evaluated from an EXACT three-way bf16 split of both operands,
 //   x = h + m + l  (h = bf16(x), m = bf16(x - h), l = x - h - m: 8 + 8 + 8 significand bits),
 //   a*b ~ m*m' + l*h' + h*l' + m*h' + h*m' + h*h'   (six v_mfma_f32_32x32x16_bf16, fp32 accumulate, smallest first);

@@ -1,4 +1,4 @@
-// csrc/gemm6s.hip: the weights-stationary K = 256 products of the bf16x6 mode, called from gemm.hip's dispatch.
+// csrc/gemm6s.hip: the weights-stationary K = 256 products of the bf16x6 mode, called from gemm_run (gemm.hip) like the launchers of gemm_common.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
-// csrc/gemm_plan.hip: the one dispatch decision of the GEMM family, read by gemm_run (gemm.hip), rlt_gemm6s_launch (gemm6s.hip),
-// rlt_gemm_workspace and rlt_gemm_plan.  Host only.
+// csrc/gemm_plan.hip: the one dispatch decision of the GEMM family, read by gemm_run (gemm.hip), the family launchers (gemm_common.h,
+// gemm6s.h), rlt_gemm_workspace and rlt_gemm_plan.  Host only.
 #pragma once
 #include <stddef.h>
 #include "../../include/rlt_hip.h"
@@ -18,7 +18,7 @@ struct GemmPlan {
 };
 GemmPlan gemm_plan(const GemmCall& c);
 
-// per kernel family (RLT_GEMM_*): output tile, workgroup size, dynamic LDS bytes.  gemm.hip / gemm6s.hip assert them against the
+// per kernel family (RLT_GEMM_*): output tile, workgroup size, dynamic LDS bytes.  Each family's file asserts its row against the
 // kernels' own constants.
 struct GemmFamily { int bm, bn, wg; size_t lds; };
 constexpr GemmFamily GEMM_FAMILY[] = {

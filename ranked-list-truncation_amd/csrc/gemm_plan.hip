@@ -1,4 +1,4 @@
-// The GEMM family's dispatch plan (host code only; the kernels are in gemm.hip and gemm6s.hip).  gemm_plan() is the one place where a
+// The GEMM family's dispatch plan (host code only; the kernels are in gemm_f32.hip, gemm3.hip and the gemm6*.hip files).  gemm_plan() is the one place where a
 // kernel family, loader form, persistent form, split, slab length, XCD pinning, gemm6s epilogue or panel form is chosen.
 //
 // The family's environment switches (A/B runs: bench.py, tools/*.sh), read once per process:

@@ -1,7 +1,7 @@
 // Path-level entry points: one call = the forward or the backward of one module of the
 // reference's models - an nn.TransformerEncoderLayer with list-axis attention (models/AttnCut.py:9-10,18;
 // models/Choopy.py:11-12,21; models/MMOECut.py:9-13) or the 2-layer bidirectional nn.LSTM(…,128) encoder
-// (models/AttnCut.py:8,17) - composed HERE from the kernel launches of gemm.hip / attention*.hip / norm.hip / lstm.hip,
+// (models/AttnCut.py:8,17) - composed HERE from the kernel launches of gemm*.hip / attention*.hip / norm.hip / lstm.hip,
 // so that a host in any language drives the hot path with two calls per module instead of re-implementing the
 // launch sequence, the in-place accumulation order and the stash reuse.  Everything is stream-ordered; the caller owns
 // the stash (forward -> backward) and the scratch workspace, whose sizes rlt_workspace_bytes() reports.

@@ -1,8 +1,9 @@
-"""Two things csrc/ must not grow back (no compilation, no GPU):
+"""Things csrc/ must not grow back (no compilation, no GPU):
 
   * compile-time A/B switches that nothing builds: every macro a preprocessor conditional under csrc/ tests is on a list written
     here - the builds a committed tool or test asks for, and nothing else;
-  * private copies of the bf16 split primitives: no .hip file defines a function that csrc/split6.h defines.
+  * private copies of the bf16 split primitives: no .hip file defines a function that csrc/split6.h defines;
+  * private copies of what the GEMM family files share: gemm_common.h, gemm3.h, gemm6c.h.
 """
 import os
 import re
@@ -49,3 +50,20 @@ def test_no_private_copy_of_a_split_primitive():
     clashes = {name: sorted(_defined_functions(text) & shared) for name, text in texts.items() if name.endswith(".hip")}
     clashes = {k: v for k, v in clashes.items() if v}
     assert not clashes, f"defined in csrc/split6.h and again in: {clashes}"
+
+
+def test_no_private_copy_of_the_gemm_frame():
+    """what the GEMM family files share is defined once: in gemm_common.h, or in the header of the family that introduced it"""
+    texts = dict(_sources())
+    shared = {h: _defined_functions(texts[h]) for h in ("gemm_common.h", "gemm3.h", "gemm6c.h")}
+    assert {"xcd_remap", "decode_block", "tile_frame", "next_tile", "gemm_epilogue", "write_output_t", "write_output", "write_output_simple", "accumulate_blocks",
+            "csum_add", "finish_colsum", "family_is"} <= shared["gemm_common.h"], sorted(shared["gemm_common.h"])
+    assert {"prow2", "swz2", "kcb_row", "load3b"} <= shared["gemm3.h"] and {"phys6"} <= shared["gemm6c.h"]
+    for header, names in shared.items():
+        clashes = {name: sorted(_defined_functions(text) & names) for name, text in texts.items() if name != header}
+        clashes = {k: v for k, v in clashes.items() if v}
+        assert not clashes, f"defined in csrc/{header} and again in: {clashes}"
+    # and the constants two files need
+    for const, header in (("BK3", "gemm3.h"), ("BM2", "gemm3.h"), ("PL2", "gemm3.h"), ("HB6", "gemm6c.h"), ("KB6", "gemm6c.h")):
+        holders = [name for name, text in texts.items() if re.search(r"constexpr\s+int\s+[^;]*\b%s\s*=" % const, text)]
+        assert holders == [header], (const, holders)

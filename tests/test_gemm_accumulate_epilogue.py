@@ -1,4 +1,4 @@
-"""The RLT_GEMM_ACCUMULATE epilogue of the bf16x6 tiles gemm6c and gemm6e (csrc/gemm.hip: accumulate_blocks), through the raw C ABI
+"""The RLT_GEMM_ACCUMULATE epilogue of the bf16x6 tiles gemm6c and gemm6e (csrc/gemm_common.h: accumulate_blocks), through the raw C ABI
 (rlt_gemm_ex), `pytest -m gpu`.  That epilogue reads C in batches ordered by hand - a block's 16 values together, the next block's
 before this block's stores - so what is to be shown is that every element still gets fl(fl(acc + bias) + C_old), ReLU after, whatever
 the tile walk, the layout of B, the leading dimension of C and whether C is the buffer an earlier GEMM wrote.

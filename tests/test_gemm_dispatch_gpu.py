@@ -1,4 +1,4 @@
-"""Every dispatch branch of the GEMM family (csrc/gemm.hip, csrc/gemm6s.hip) through the raw C ABI (rlt_hip.native), `pytest -m gpu`.
+"""Every dispatch branch of the GEMM family (csrc/gemm.hip and the family files it dispatches to: gemm_f32, gemm3, gemm6, gemm6c, gemm6e, gemm6s) through the raw C ABI (rlt_hip.native), `pytest -m gpu`.
 One test id per (kernel family, operand layout, variant, operand kind; the table: tests/gemm_cases.py); the id names the branch, and
 rlt_gemm_last_dispatch - what the library itself recorded where it launched, and what rlt_gemm_plan returns for the same call - is
 ASSERTED against it, so a moved threshold fails with "expected gemm6b, got
@@ -227,7 +227,7 @@ def epilogue_inputs(c, exact, g):
 
 
 def reference(N, c, AB, epi):
-    """the epilogue of gemm_epilogue (csrc/gemm.hip) in float64: bias, accumulate, ReLU, mask * mask_scale, dropout"""
+    """the epilogue of gemm_epilogue (csrc/gemm_common.h) in float64: bias, accumulate, ReLU, mask * mask_scale, dropout"""
     M, Nn = c["M"], c["N"]
     v = AB.clone()
     if c.get("bias"):
